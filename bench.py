@@ -18,12 +18,21 @@ Workloads (BASELINE.json configs); fp64 throughout (>= the refer
       rounding residue taken as 0): with the reference gate its trajectory depends on the summation order, hence
       on the rank count (the oracle alone ends after 4 or 7 iterations depending on its thread count,
       profiles/r03_c4_oracle_gate_envelope.json); in gate_mode 1 every rank count runs the same trajectory
-      (tests/test_multirank_gpu.py).  The N = 1 line carries C4 on one GPU ("c4_1gpu") and each rank's share of
-      C4 sharded 2, 4 and 8 ways solved alone ("c4_shards_1gpu": the per-rank work without the all-reduce).
+      (tests/test_multirank_gpu.py).  c4_speedup_vs_1gpu is part of a --full run, whose N = 1 line carries C4 on
+      one GPU ("c4_1gpu") and each rank's share of C4 sharded 2, 4 and 8 ways solved alone ("c4_shards_1gpu":
+      the per-rank work without the all-reduce).
   C3w (--workload C3w, a side measurement, never the default) one C3-sized shard per GPU: a window of
       50 000 N landmarks ("scaling": "weak"), value = N x (LM iterations of the window) / s.
 
-Usage: python bench.py [--gpus N --steps K --warmup W] [--workload C3|C3w|C4]
+A plain run does what value needs and no more: set up, warm up, time the K steps, print the line.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
+--full adds everything else the benchmark measures or checks, each in runs of its own after the timed
+region: the per-kernel times and the k_lin roofline, the N > 1 line's C4-on-one-GPU base, and on one GPU
+the side measurements (host-buffer path, C4 and its shards, the live configuration, PCG, fp32 residuals,
+longer windows, frontend, LK) and the CPU baseline with the oracle comparisons (--no-extras and --no-cpu
+drop the last two).
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--workload C3|C3w|C4] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -238,6 +247,56 @@ def time_solves(solver, steps, barrier):
     return time.perf_counter() - t0, it, tr, res
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000   # --dump-outputs writes at most this much, over all ranks
+DUMP_SAMPLE_SEED = 0
+SUMMARY_FIELDS = ("iterations", "trials", "accepted", "chi2_initial", "chi2_final", "lambda_final")
+
+
+def fit_dump_budget(arrays, budget):
+    """The arrays to write, at most `budget` bytes in all: every array that is small (at most 1/16 of the
+    budget) whole, and of the others, when the sum is over the budget, a fixed sample of rows (the same
+    seeded choice for the same shape, in ascending row order) scaled so that the sum fits."""
+    small = {k: a for k, a in arrays.items() if a.nbytes <= budget // 16}
+    big = {k: a for k, a in arrays.items() if k not in small}
+    total = sum(a.nbytes for a in arrays.values())
+    if total <= budget:
+        return dict(arrays)
+    scale = (budget - sum(a.nbytes for a in small.values())) / sum(a.nbytes for a in big.values())
+    out = dict(small)
+    for k, a in big.items():
+        rows = int(a.shape[0] * scale)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], size=rows, replace=False))
+        out[k] = a[idx]
+    return {k: out[k] for k in arrays}
+
+
+def dump_outputs(dirname, solver, last, rank, world):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy (float64).  The timed call is the
+    array-free solve, whose caller receives the summary scalars and the LM trace: summary.npy (SUMMARY_FIELDS in
+    that order), trace_chi2.npy, trace_lambda.npy, taken from the last timed step itself.  The states that
+    solve ended on stay on the device, so the resident window is solved once more with the output arrays
+    requested (the same restart from the uploaded state, the same kernels; a collective call with N > 1):
+    pose_Tcw.npy [P, 12], lm_xyz.npy [L, 3], edge_robust_chi2.npy [O].  That solve must repeat the last timed
+    step's summary and trace exactly, else nothing is written.  With N > 1 the poses are replicated and
+    rank r > 0 writes its landmark shard as lm_xyz.rank<r>.npy and edge_robust_chi2.rank<r>.npy."""
+    full = solver.solve_resident(want_states=True, want_edges=True)
+    summary = np.array([last[f] for f in SUMMARY_FIELDS], np.float64)
+    same = (np.array_equal(summary, np.array([full[f] for f in SUMMARY_FIELDS], np.float64), equal_nan=True)
+            and np.array_equal(last["trace_chi2"], full["trace_chi2"], equal_nan=True)
+            and np.array_equal(last["trace_lambda"], full["trace_lambda"], equal_nan=True))
+    if not same:
+        raise SystemExit("--dump-outputs: the solve with output arrays did not repeat the last timed step "
+                         f"({[last[f] for f in SUMMARY_FIELDS]} vs {[full[f] for f in SUMMARY_FIELDS]})")
+    arrays = {"lm_xyz": full["lm_xyz"], "edge_robust_chi2": full["edge_robust_chi2"]}
+    if rank == 0:
+        arrays = dict(summary=summary, trace_chi2=last["trace_chi2"], trace_lambda=last["trace_lambda"],
+                      pose_Tcw=full["pose_Tcw"], **arrays)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in fit_dump_budget(arrays, DUMP_BUDGET_BYTES // world).items():
+        name = k if rank == 0 else f"{k}.rank{rank}"
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def rocprof_k_lin(cfg_key):
     """k_lin durations from the committed rocprofv3 kernel trace of this bench (scripts/rocprof_k_lin.py):
     the same back-to-back replays the live timing uses, and the launches inside the timed solves."""
@@ -277,7 +336,7 @@ def roofline(solver, n_obs, n_lm, k, cfg_key, reps=50):
              "frac": round(gbs / HBM_PEAK_GBS, 4), "bytes_per_launch": nbytes, "traffic": traffic})
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # 1000 C3 solves is ~1.1 s of GPU work: long enough for the driver's utilisation sampling to see it
@@ -287,15 +346,21 @@ def main():
                     help="auto: C3 on one GPU, C4 (BASELINE config 4, landmark-sharded, strong scaling) over N > 1")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--family", default="stable_noout", choices=["stable_noout", "stable", "default"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed line (no side measurements)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: per-kernel "
+                         "times, the k_lin roofline, the side measurements and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: the timed line with its per-kernel times and roofline (no side measurements)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="length of the cpu_baseline sample")
     ap.add_argument("--trials-per-sync", type=int, default=0)
     ap.add_argument("--comm", default="rccl", choices=["rccl", "host", "p2p"],
                     help="per-trial exchange with N > 1: RCCL over xGMI (the default), the one-shot peer-write "
                          "exchange on the device (LH_COMM_P2P: IPC-mapped buffers, bootstrap over gloo), or the "
                          "ABI's host transport over gloo (a rehearsal of the N-rank flow on fewer GPUs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -346,21 +411,25 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # the same solves with a HIP event pair around every kernel: per-kernel ms per solve
-    solver.set_profiling(True)
-    solver.kernel_stats_reset()
-    time_solves(solver, max(2, min(20, args.steps // 4)), barrier)
-    ks = solver.kernel_stats()
-    solver.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, last, rank, world)
     n_obs, n_lm = len(w["obs_pose"]), len(w["lm_xyz"])
     c = WORKLOADS[name]
-    cfg_key = f"{name}-{args.family}-s{args.seed}" + (f"-x{world}" if WORKLOADS[name].get("per_rank") else "")
-    rl, rl_hbm = roofline(solver, n_obs, n_lm, c["k"], cfg_key)
+    ks = rl = rl_hbm = None
+    if args.full:
+        # the same solves with a HIP event pair around every kernel: per-kernel ms per solve
+        solver.set_profiling(True)
+        solver.kernel_stats_reset()
+        time_solves(solver, max(2, min(20, args.steps // 4)), barrier)
+        ks = solver.kernel_stats()
+        solver.set_profiling(False)
+        cfg_key = f"{name}-{args.family}-s{args.seed}" + (f"-x{world}" if WORKLOADS[name].get("per_rank") else "")
+        rl, rl_hbm = roofline(solver, n_obs, n_lm, c["k"], cfg_key)
 
     # C4 on N > 1 GPUs: the same window on rank 0's GPU alone (one rank, the same gate mode and trajectory), the
     # base of c4_speedup_vs_1gpu; the other ranks wait at the barrier below
     c4_one = None
-    if name == "C4" and world > 1 and rank == 0:
+    if args.full and name == "C4" and world > 1 and rank == 0:
         w1 = make_window("C4", args.family, args.seed, 0, 1)
         s1 = lego_ba.Solver(device=local, gate_mode=1, trials_per_sync=args.trials_per_sync)
         s1.upload(w1)
@@ -422,16 +491,17 @@ def main():
         "trials_per_s": round(trials / dt, 3),
         "ms_per_trial": round(dt / trials * 1e3, 5),
         "chi2_final": last["chi2_final"],
-        "kernels_ms_per_solve_event_bracketed": {k: round(v[1] / nprof, 4) for k, v in ks.items()},
-        "roofline": rl,
-        "roofline_hbm": rl_hbm,
     }
+    if args.full:
+        out["kernels_ms_per_solve_event_bracketed"] = {k: round(v[1] / nprof, 4) for k, v in ks.items()}
+        out["roofline"] = rl
+        out["roofline_hbm"] = rl_hbm
     if c4_one is not None:
         out["c4_1gpu_same_job"] = c4_one
         out["c4_speedup_vs_1gpu"] = round((iters / dt) / c4_one["iterations_per_s"], 3)
         out["c4_speedup_note"] = ("C4's LM iterations/s on the N GPUs over the same window's on rank 0's GPU alone "
                                   "(measured in this job after the timed region): the strong-scaling speedup")
-    if world > 1 or args.no_extras:
+    if world > 1 or args.no_extras or not args.full:
         print(json.dumps(out))
         if dist is not None:
             dist.barrier()

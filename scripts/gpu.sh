@@ -5,8 +5,8 @@
 #
 #   tests[=FILES]      pytest -m gpu on FILES (default: tests/), verbose, per-test timeout
 #   smoke              __graft_entry__.smoke()
-#   bench[=ARGS]       bench.py ARGS (default: the contract's default run, CPU baseline included)
-#   quick              bench.py --steps 200 --warmup 3 --no-cpu --no-extras
+#   bench[=ARGS]       bench.py ARGS (default: --full, the default run with every side measurement and the CPU baseline)
+#   quick              bench.py --full --steps 200 --warmup 3 --no-cpu --no-extras (the timed line, per-kernel times, roofline)
 #   trace              rocprofv3 --kernel-trace --stats of the quick bench (per-kernel averages)
 #   pmc                the PMC passes over the quick bench (one counter group per run)
 #   stamps=CFG         k_ctrl phase stamps (diagnostic -DLH_STAMPS library) on window CFG (C3, P64, ...)
@@ -22,7 +22,7 @@ TAG=${TAG:-run}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-QUICK="bench.py --steps 200 --warmup 3 --no-cpu --no-extras"
+QUICK="bench.py --full --steps 200 --warmup 3 --no-cpu --no-extras"
 SFX=""
 
 kstats() {   # label, rocprof output dir -> one summary line per kernel of interest
@@ -52,7 +52,7 @@ for step in "$@"; do
         timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { cat "$OUT/smoke.log"; exit 1; }
         cat "$OUT/smoke.log" ;;
     bench)
-        timeout -k 10 600 python3 bench.py $arg > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+        timeout -k 10 600 python3 bench.py ${arg:---full} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
         tail -c 600 "$OUT/bench.json" ;;
     quick)
         timeout -k 10 300 python3 $QUICK > "$OUT/quick$SFX.json" 2> "$OUT/quick$SFX.err" || { tail -20 "$OUT/quick$SFX.err"; exit 1; }
@@ -67,7 +67,7 @@ for step in "$@"; do
         pass() {   # name, counters...
             local nm=$1; shift
             timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -d "$OUT/pmc/$nm" -o $nm --output-format csv -- \
-                python3 bench.py --steps 3 --warmup 1 --no-cpu --no-extras > "$OUT/pmc/$nm.log" 2>&1
+                python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras > "$OUT/pmc/$nm.log" 2>&1
         }
         pass sq SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS || exit 1
         pass sq2 SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INSTS_VALU_FMA_F64 SQ_BUSY_CYCLES || exit 1

@@ -1,5 +1,5 @@
-"""k_lin launch durations from a rocprofv3 --kernel-trace of `bench.py --no-extras` (scripts/gpu_r02.sh
-prof stage): the bench's back-to-back replays (its live roofline timing, the last `reps` launches)
+"""k_lin launch durations from a rocprofv3 --kernel-trace of `bench.py --full --no-extras` (scripts/gpu.sh
+trace): the bench's back-to-back replays (its live roofline timing, the last `reps` launches)
 and the launches inside the timed solves (after k_ctrl).  Excluded by duration: launches enqueued
 past the device's stop (they exit at once, < 10 us) and the final iteration's evaluate-only launches
 (ctrl.evo, ~15 us): neither is the per-trial linearisation the roofline prices.  Writes the JSON bench.py reports beside its live

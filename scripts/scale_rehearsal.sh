@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 300 python3 bench.py --steps 100 --warmup 2 --no-cpu --no-extras > "$OUT/n1.json" 2> "$OUT/n1.err" || { tail -20 "$OUT/n1.err"; exit 1; }
 for comm in host p2p; do
     timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29502 bench.py --gpus 2 --steps 10 --warmup 1 --comm $comm \
+        --master-port 29502 bench.py --full --gpus 2 --steps 10 --warmup 1 --comm $comm \
         > "$OUT/n2_$comm.json" 2> "$OUT/n2_$comm.err" || { tail -20 "$OUT/n2_$comm.err"; exit 1; }
 done
 for n in 1 2_host 2_p2p; do python3 -c "
