@@ -276,7 +276,7 @@ LH_HD static inline int lh_ctrl_units(int n, const int32_t* tile_fcb, const int*
 
 // k_ctrl_b's band image (prm.bimg): tile row I (rows 16 I .. 16 I + 15) holds columns 16 (I - 7) .. 16 I + 15,
 // 128 per row, the order k_ctrl_b's stream loaders read (a banded window's rows start at or after column
-// 16 I - 104, lh_host.cpp); two copies (staged, committed) of ceil16(6P) / 16 tile rows each
+// 16 I - 104, lh_plan.cpp solve_config); two copies (staged, committed) of ceil16(6P) / 16 tile rows each
 #define LH_BIMG_TR (16 * 128)
 LH_HD static inline int lh_bimg_idx(int r, int c) {
     const int I = r >> 4;
@@ -298,7 +298,7 @@ struct lh_peers {
     double* p[LH_P2P_MAX];   // every rank's exchange buffer, mapped into this process (p[rank]: its own)
 };
 
-// k_ctrl_b's per-window tables (bblk null: no banded controller for this window)
+// k_ctrl_b's per-window tables: lh_band_args below (all null unless the window's kind is LH_CTRL_BAND)
 // The restart of a resident solve, done by the initial linearisation's block 0 (k_lin<T, false>): controller
 // zeroed, both pose and pose-table buffers from their initial copies, the step zeroed; its chunks read the
 // landmarks straight from the window (lm_perm, lm_in) and the initial tables from ptab_init.
@@ -309,6 +309,10 @@ struct lh_reset_args {
     const double* ptab_init;   // [2][P * ncam * LH_PT] initial pose tables (both slots)
     int nqt, nptab, ndxp;
 };
+
+// the controller kernel a window runs (lh_plan.h solve_config decides; lh_launch_ctrl switches on it;
+// lh_debug_controller's low byte): k_ctrl, k_dense + k_ctrl_g, k_ctrl_p, k_ctrl_b
+enum lh_ctrl_kind { LH_CTRL_LDS = 0, LH_CTRL_DENSE = 1, LH_CTRL_PCG = 2, LH_CTRL_BAND = 3 };
 
 struct lh_band_args {
     const int32_t* bblk;     // [P * 64] block of pose pair (p, p + d), -1 if absent

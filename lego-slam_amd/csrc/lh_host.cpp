@@ -53,7 +53,7 @@ hipError_t lh_launch_ctrl(hipStream_t st, lh_ctrl* ctrl, double* rs_commit, cons
                           const uint32_t* rsmap, const uint16_t* pair_pq, double* dxp, lh_params prm, int mode,
                           int* host_done, int seq, double* gA, const double* gS,
                           const int32_t* brow_ptr, const uint32_t* brow_ent, const uint16_t* units, lh_band_args band,
-                          double* img);
+                          double* img, int kind);
 hipError_t lh_launch_dense(hipStream_t st, const double* rs_stage, const uint16_t* pair_pq, const lh_ctrl* ctrl,
                            double* gS, int P);
 hipError_t lh_launch_gather(hipStream_t st, const lh_ctrl* ctrl, const double* rec, const int32_t* lm_perm, int nrec,
@@ -300,12 +300,8 @@ struct lh_handle {
     int n_red = 0;   // k_reduce's pair blocks (d_red: 4 words each, then the scalar block's sentinel)
     View<uint16_t> d_pair_pq, d_units, d_bunits;
     View<int32_t> d_bblk;
-    DevBuf<double> d_band;        // k_ctrl_b: L rows (ceil16(6P) x 128) | ND per block (steps x 64), per ladder rung
-    size_t lad_stride = 0;        // doubles of d_gA per ladder rung (k_ctrl_g, k_ctrl_p)
-    bool band = false;            // this window's LDL^T runs in k_ctrl_b
-    bool band_narrow = false;     // ... and every row's envelope starts within 56 rows of its 8-row block
-    bool band_lu = false;         // ... and some step needs the stream loaders as unit waves too
-    lh_ctrl_nd nd{};              // k_ctrl's two-chain schedule (nd.nsteps 0: the one-chain one)
+    DevBuf<double> d_band;        // k_ctrl_b's scratch per ladder rung (lh::band_scratch)
+    lh::SolveConfig cfg;          // how the uploaded window is solved (lh::solve_config): the controller kind and its sizes
     View<int32_t> d_lm_perm;
     View<double> d_ptab_init, d_qt_init, d_ext;
     DevBuf<uint8_t> d_arena;
@@ -482,7 +478,7 @@ int p2p_setup(lh_handle* h);
 // behind it, or the next upload could rewrite (or reallocate) the staging while that DMA still reads
 // it: the error returns (LH_E_UNSUPPORTED envelope checks, a failed HIP call) record it here.
 //
-// A sharded upload holds one collective, the MAX all-reduce of the envelope of S (upload_body).  A rank that fails before it (a bad pixel, an unsupported window, an allocation)
+// A sharded upload holds one collective, the MAX all-reduce of the envelope of S (envelope_collective).  A rank that fails before it (a bad pixel, an unsupported window, an allocation)
 // still joins it, contributing its status in word 0 and nothing to the envelope, so the healthy ranks
 // are not left blocked in it: every rank then returns the largest status of any rank.
 //
@@ -517,14 +513,25 @@ int upload_impl(lh_handle* h, const lh_window* w, bool sync) {
     return st;
 }
 
-int upload_body(lh_handle* h, const lh_window* w, bool sync) {
-    const double t0 = now_ms();
-    h->uploaded = false;
+// ---- the stages of an upload, in upload_body's order.  None of them decides how the window is solved:
+//      that is lh::solve_config (lh_plan.h), whose result the handle keeps (h->cfg). ----
+#define STAGE(x)                                                                                         \
+    do {                                                                                                 \
+        const int st_ = (x);                                                                             \
+        if (st_ != LH_OK) return st_;                                                                    \
+    } while (0)
+
+// the previous upload's copies out of the pinned staging
+int wait_staging(lh_handle* h) {
     if (h->staging_pending) {
         HIPCHK(spin_wait(h->ev_staging));
         h->staging_pending = false;
     }
-    // the landmark positions need no plan: they go out first and cross the link while the planner runs
+    return LH_OK;
+}
+
+// the landmark positions need no plan: they go out first and cross the link while the planner runs
+int send_landmarks(lh_handle* h, const lh_window* w) {
     if (w && w->n_landmarks > 0 && w->lm_xyz) {
         const size_t nl = 3 * (size_t)w->n_landmarks;
         HIPCHK(h->d_lm_in.ensure(nl));
@@ -533,42 +540,24 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
         par_copy(h, &seg, 1);
         HIPCHK(hipMemcpyAsync(h->d_lm_in.p, h->s_lm.p, nl * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
+    return LH_OK;
+}
+
+int plan_window(lh_handle* h, const lh_window* w) {
     lh::PlanCfg cfg;
     cfg.chunk_lm = h->opt.chunk_landmarks;
-    lh::Plan& pl = h->plan;
-    const bool sharded = h->host_comm || h->comm || h->p2p;
     cfg.rank_invariant_pairs = h->opt.world_size > 1;
-    int st = lh::plan_structure(w, cfg, h->opt.world_size > 1, pl, h->pool);
+    const int st = lh::plan_structure(w, cfg, h->opt.world_size > 1, h->plan, h->pool);
     if (st != LH_OK) {
         HIPCHK(hipEventRecord(h->ev_staging, h->stream));
         h->staging_pending = true;
-        return st;
     }
-    // Pose p's first coupled pose: the lowest pose of any chunk window holding p (a chunk writes a block
-    // for every pair of its window).  It gives the envelope of S in natural pose order, from which k_ctrl's
-    // and k_ctrl_b's work units and the banded controller's eligibility follow; a sharded solve factors
-    // the sum of every rank's blocks, so it takes the union over the ranks (below, after every rank-local
-    // failure point).
-    std::vector<int> pf(pl.P);
-    for (int p = 0; p < pl.P; ++p) pf[p] = p;
-    for (size_t c = 0; c < pl.chunk_mask.size(); ++c) {
-        const uint64_t m = pl.chunk_mask[c];
-        if (!m) continue;
-        const int lo = pl.chunk_base[c] + __builtin_ctzll(m);
-        for (uint64_t b = m; b; b &= b - 1) {
-            const int p = pl.chunk_base[c] + __builtin_ctzll(b);
-            pf[p] = std::min(pf[p], lo);
-        }
-    }
-    // past LH_PMAX poses: LDL^T by k_ctrl_b when the reduced system is banded in natural pose order
-    // (any P up to LH_PMAX_ANY), else by k_ctrl_g (dense, up to LH_PMAX_WIN poses); PCG by k_ctrl_p
-    // (block-sparse, up to LH_PMAX_ANY).  Decided after the union below; the arena reserves the band's
-    // tables whenever it may run.
-    static const int kBandSteps = 6 * LH_PMAX_ANY / 8;
-    const bool band_possible = pl.P > LH_PMAX && h->opt.linear_solver == LH_SOLVER_LDLT && !getenv("LH_NO_BAND");
-    h->band = false;
-    h->band_narrow = false;
-    h->band_lu = false;
+    return st;
+}
+
+// what this rank's share of the window must fit, whatever the other ranks hold
+int rank_local_limits(lh_handle* h) {
+    const lh::Plan& pl = h->plan;
     // k_lin's write-through record stores address both record buffers through one buffer descriptor
     // (32-bit byte offsets): up to ~8.3 M landmarks per rank
     if ((size_t)2 * pl.n_rec * LH_REC * sizeof(double) > (size_t)INT32_MAX) return LH_E_UNSUPPORTED;
@@ -576,61 +565,73 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
     for (int T = 1; T <= LH_TMAX; ++T)
         if (pl.tgroup_begin[T + 1] > pl.tgroup_begin[T] && lh_lin_smem(T, pl.ncam) > (size_t)h->lds_limit)
             return LH_E_UNSUPPORTED;
+    return LH_OK;
+}
+
+// The per-window tables (all but the observation slots and the positions) live in one arena, on the
+// device and in pinned staging, at the same offsets: they cross the link as one copy.  Each
+// hipMemcpyAsync costs ~10 us of DMA-engine turnaround beside its transfer (rocprofv3 memory-copy
+// trace of lh_upload), and the 13 small copies these were made most of the upload's tail.
+// band_possible: the window may run banded (decided after the envelope collective), so k_ctrl_b's
+// tables are reserved.
+int bind_arena(lh_handle* h, bool band_possible) {
+    const lh::Plan& pl = h->plan;
     const int P = pl.P, ncam = pl.ncam;
     h->P = P; h->L = pl.L; h->O = pl.O; h->ncam = ncam;
     h->n_rec = pl.n_rec;
     h->n_slots = pl.n_slots;
     h->LY = lh_rs_make(P, pl.npairs);
-
-    // ---- device buffers (before the fill: its slot batches are copied as they complete) ----
     const size_t PT = (size_t)P * ncam * LH_PT;
-    // The per-window tables (all but the observation slots and the positions) live in one arena, on the
-    // device and in pinned staging, at the same offsets: they cross the link as one copy.  Each
-    // hipMemcpyAsync costs ~10 us of DMA-engine turnaround beside its transfer (rocprofv3 memory-copy
-    // trace of lh_upload), and the 13 small copies these were made most of the upload's tail.
-    {
-        size_t bytes = 0;
-        auto part = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
-        const size_t o_chunks = part(pl.n_chunks * sizeof(lh_chunk)), o_sbs = part((size_t)pl.n_sb * sizeof(lh_subbatch));
-        const size_t o_lmp = part((size_t)pl.n_rec * sizeof(int32_t)), o_pptr = part(((size_t)pl.npairs + 1) * sizeof(uint32_t));
-        const size_t o_items = part((size_t)pl.n_items * sizeof(uint32_t)), o_ppq = part(2 * (size_t)pl.npairs * sizeof(uint16_t));
-        const size_t o_rsmap = part((size_t)pl.npairs * 36 * sizeof(uint32_t)), o_ptab = part(2 * PT * sizeof(double));
-        const size_t o_qt = part(24 * (size_t)std::max(P, 1) * sizeof(double)), o_ext = part(LH_EXT * (size_t)ncam * sizeof(double));
-        const size_t o_fix = part(pl.fixed_bits.size() * sizeof(uint64_t)), o_bptr = part(pl.brow_ptr.size() * sizeof(int32_t));
-        const size_t o_bent = part(pl.brow_ent.size() * sizeof(uint32_t));
-        const size_t o_units = part(16 * LH_NSTEP * sizeof(uint16_t));
-        const size_t n_bunits = band_possible ? 16 * (size_t)kBandSteps : 0, n_bblk = band_possible ? (size_t)P * 64 : 0;
-        const size_t o_bunits = part(n_bunits * sizeof(uint16_t));
-        const size_t o_bblk = part(n_bblk * sizeof(int32_t));
-        const size_t o_red = part(4 * ((size_t)pl.npairs + 1) * sizeof(uint32_t));
-        HIPCHK(h->d_arena.ensure(bytes));
-        HIPCHK(h->s_arena.ensure(bytes));
-        h->arena_bytes = bytes;
-        auto bind = [](auto& d, auto& st, uint8_t* dbase, uint8_t* sbase, size_t off, size_t count) {
-            using T = std::remove_pointer_t<decltype(d.p)>;
-            d.p = reinterpret_cast<T*>(dbase + off); d.n = count;
-            st.p = reinterpret_cast<T*>(sbase + off); st.n = count;
-        };
-        uint8_t* db = h->d_arena.p;
-        uint8_t* sb = h->s_arena.p;
-        bind(h->d_chunks, h->s_chunks, db, sb, o_chunks, pl.n_chunks);
-        bind(h->d_sbs, h->s_sbs, db, sb, o_sbs, pl.n_sb);
-        bind(h->d_lm_perm, h->s_lm_perm, db, sb, o_lmp, pl.n_rec);
-        bind(h->d_pair_ptr, h->s_pair_ptr, db, sb, o_pptr, pl.npairs + 1);
-        bind(h->d_items, h->s_items, db, sb, o_items, pl.n_items);
-        bind(h->d_pair_pq, h->s_pair_pq, db, sb, o_ppq, 2 * (size_t)pl.npairs);
-        bind(h->d_rsmap, h->s_rsmap, db, sb, o_rsmap, (size_t)pl.npairs * 36);
-        bind(h->d_ptab_init, h->s_ptab, db, sb, o_ptab, 2 * PT);
-        bind(h->d_qt_init, h->s_qt, db, sb, o_qt, 24 * (size_t)std::max(P, 1));
-        bind(h->d_ext, h->s_ext, db, sb, o_ext, LH_EXT * (size_t)ncam);
-        bind(h->d_fixed, h->s_fixed, db, sb, o_fix, pl.fixed_bits.size());
-        bind(h->d_brow_ptr, h->s_brow_ptr, db, sb, o_bptr, pl.brow_ptr.size());
-        bind(h->d_brow_ent, h->s_brow_ent, db, sb, o_bent, pl.brow_ent.size());
-        bind(h->d_units, h->s_units, db, sb, o_units, 16 * LH_NSTEP);
-        bind(h->d_bunits, h->s_bunits, db, sb, o_bunits, n_bunits);
-        bind(h->d_bblk, h->s_bblk, db, sb, o_bblk, n_bblk);
-        bind(h->d_red, h->s_red, db, sb, o_red, 4 * ((size_t)pl.npairs + 1));
-    }
+    size_t bytes = 0;
+    auto part = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
+    const size_t o_chunks = part(pl.n_chunks * sizeof(lh_chunk)), o_sbs = part((size_t)pl.n_sb * sizeof(lh_subbatch));
+    const size_t o_lmp = part((size_t)pl.n_rec * sizeof(int32_t)), o_pptr = part(((size_t)pl.npairs + 1) * sizeof(uint32_t));
+    const size_t o_items = part((size_t)pl.n_items * sizeof(uint32_t)), o_ppq = part(2 * (size_t)pl.npairs * sizeof(uint16_t));
+    const size_t o_rsmap = part((size_t)pl.npairs * 36 * sizeof(uint32_t)), o_ptab = part(2 * PT * sizeof(double));
+    const size_t o_qt = part(24 * (size_t)std::max(P, 1) * sizeof(double)), o_ext = part(LH_EXT * (size_t)ncam * sizeof(double));
+    const size_t o_fix = part(pl.fixed_bits.size() * sizeof(uint64_t)), o_bptr = part(pl.brow_ptr.size() * sizeof(int32_t));
+    const size_t o_bent = part(pl.brow_ent.size() * sizeof(uint32_t));
+    const size_t o_units = part(16 * LH_NSTEP * sizeof(uint16_t));
+    const size_t n_bunits = band_possible ? 16 * (size_t)lh::kBandSteps : 0, n_bblk = band_possible ? (size_t)P * 64 : 0;
+    const size_t o_bunits = part(n_bunits * sizeof(uint16_t));
+    const size_t o_bblk = part(n_bblk * sizeof(int32_t));
+    const size_t o_red = part(4 * ((size_t)pl.npairs + 1) * sizeof(uint32_t));
+    HIPCHK(h->d_arena.ensure(bytes));
+    HIPCHK(h->s_arena.ensure(bytes));
+    h->arena_bytes = bytes;
+    auto bind = [](auto& d, auto& st, uint8_t* dbase, uint8_t* sbase, size_t off, size_t count) {
+        using T = std::remove_pointer_t<decltype(d.p)>;
+        d.p = reinterpret_cast<T*>(dbase + off); d.n = count;
+        st.p = reinterpret_cast<T*>(sbase + off); st.n = count;
+    };
+    uint8_t* db = h->d_arena.p;
+    uint8_t* sb = h->s_arena.p;
+    bind(h->d_chunks, h->s_chunks, db, sb, o_chunks, pl.n_chunks);
+    bind(h->d_sbs, h->s_sbs, db, sb, o_sbs, pl.n_sb);
+    bind(h->d_lm_perm, h->s_lm_perm, db, sb, o_lmp, pl.n_rec);
+    bind(h->d_pair_ptr, h->s_pair_ptr, db, sb, o_pptr, pl.npairs + 1);
+    bind(h->d_items, h->s_items, db, sb, o_items, pl.n_items);
+    bind(h->d_pair_pq, h->s_pair_pq, db, sb, o_ppq, 2 * (size_t)pl.npairs);
+    bind(h->d_rsmap, h->s_rsmap, db, sb, o_rsmap, (size_t)pl.npairs * 36);
+    bind(h->d_ptab_init, h->s_ptab, db, sb, o_ptab, 2 * PT);
+    bind(h->d_qt_init, h->s_qt, db, sb, o_qt, 24 * (size_t)std::max(P, 1));
+    bind(h->d_ext, h->s_ext, db, sb, o_ext, LH_EXT * (size_t)ncam);
+    bind(h->d_fixed, h->s_fixed, db, sb, o_fix, pl.fixed_bits.size());
+    bind(h->d_brow_ptr, h->s_brow_ptr, db, sb, o_bptr, pl.brow_ptr.size());
+    bind(h->d_brow_ent, h->s_brow_ent, db, sb, o_bent, pl.brow_ent.size());
+    bind(h->d_units, h->s_units, db, sb, o_units, 16 * LH_NSTEP);
+    bind(h->d_bunits, h->s_bunits, db, sb, o_bunits, n_bunits);
+    bind(h->d_bblk, h->s_bblk, db, sb, o_bblk, n_bblk);
+    bind(h->d_red, h->s_red, db, sb, o_red, 4 * ((size_t)pl.npairs + 1));
+    return LH_OK;
+}
+
+// the device buffers sized by the window alone (before the fill: its slot batches are copied as they
+// complete); ladder: one pending step per lambda-ladder rung
+int window_buffers(lh_handle* h, int ladder) {
+    const lh::Plan& pl = h->plan;
+    const int P = pl.P;
+    const size_t PT = (size_t)P * pl.ncam * LH_PT;
     HIPCHK(h->d_meta.ensure(pl.n_slots));
     HIPCHK(h->d_uv.ensure(2 * pl.n_slots));
     HIPCHK(h->d_obs_perm.ensure(pl.n_slots));
@@ -642,22 +643,19 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
     HIPCHK(h->d_rows.ensure((size_t)pl.n_items * LH_ROW));
     HIPCHK(h->d_rs_stage.ensure(h->LY.total));
     HIPCHK(h->d_rs_commit.ensure(h->LY.total));
-    // the lambda ladder's rungs, one controller workgroup each (LH_NO_LADDER=1: one rung, the A/B
-    // switch): one pending step per rung, and per rung the controller's global scratch
-    const int ladder = !getenv("LH_NO_LADDER") ? std::max(1, std::min(h->opt.max_trials, LH_LAD)) : 1;
-    h->lad_stride = 0;
-    if (P > LH_PMAX && h->opt.linear_solver == LH_SOLVER_PCG) {   // k_ctrl_p's row-contiguous copy of S (36 per block-row entry)
-        h->lad_stride = pl.brow_ent.size() * 36;
-        HIPCHK(h->d_gA.ensure((size_t)ladder * h->lad_stride));
-    }
     HIPCHK(h->d_maxd.ensure(1));
     HIPCHK(h->d_dxp.ensure((size_t)ladder * 6 * (size_t)std::max(P, 1)));
     HIPCHK(h->d_ctrl.ensure(1));
     HIPCHK(h->d_out_xyz.ensure(3 * (size_t)pl.L));
     HIPCHK(h->d_out_rho.ensure(pl.O));
     if (h->host_comm) HIPCHK(h->s_rs.ensure(h->LY.total + 1));
+    return LH_OK;
+}
 
-    // ---- staging and the fill ----
+// the planner's fill into the staging (the observation slots go out as they complete), k_reduce's
+// block table, and the plan's small tables
+int fill_staging(lh_handle* h, const lh_window* w, const lh::Switches& sw) {
+    const lh::Plan& pl = h->plan;
     HIPCHK(h->s_meta.ensure(pl.n_slots));
     HIPCHK(h->s_uv.ensure(2 * pl.n_slots));
     HIPCHK(h->s_obs_perm.ensure(pl.n_slots));
@@ -673,35 +671,26 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
         return fs;
     }
     std::memcpy(h->s_pair_ptr.p, pl.pair_ptr.data(), pl.pair_ptr.size() * sizeof(uint32_t));
-    // k_reduce's blocks: one per pose pair that some chunk's rows reach ({block, first row, end row, p | q << 16}),
-    // then the scalar block's sentinel.  One rank skips the pairs no chunk couples: their blocks of S are zero
-    // for the whole window (the reduced-system buffers are cleared per window, below).  A sharded solve keeps
-    // every pair: a rank's empty pair still has to write its zero contribution over last trial's all-reduced sum.
-    {
-        const bool skip = h->opt.world_size == 1 && !getenv("LH_NO_RED_SKIP");
-        uint32_t* rt = h->s_red.p;
-        int k = 0;
-        for (int b = 0; b < pl.npairs; ++b) {
-            const uint32_t ib = pl.pair_ptr[b], ie = pl.pair_ptr[b + 1];
-            if (skip && ib == ie) continue;
-            rt[4 * k] = (uint32_t)b; rt[4 * k + 1] = ib; rt[4 * k + 2] = ie;
-            rt[4 * k + 3] = (uint32_t)pl.pair_list[2 * b] | ((uint32_t)pl.pair_list[2 * b + 1] << 16);
-            ++k;
-        }
-        rt[4 * k] = (uint32_t)pl.npairs; rt[4 * k + 1] = 0; rt[4 * k + 2] = 0; rt[4 * k + 3] = 0;
-        h->n_red = k;
-        if (skip) {   // the skipped pairs' blocks (and every buffer slot k_reduce never writes) read as zero
-            HIPCHK(hipMemsetAsync(h->d_rs_stage.p, 0, h->LY.total * sizeof(double), h->stream));
-            HIPCHK(hipMemsetAsync(h->d_rs_commit.p, 0, h->LY.total * sizeof(double), h->stream));
-        }
+    const bool skip = lh::reduce_skip(h->opt.world_size, sw);
+    h->n_red = lh::reduce_table(pl, skip, h->s_red.p);
+    if (skip) {   // the skipped pairs' blocks (and every buffer slot k_reduce never writes) read as zero
+        HIPCHK(hipMemsetAsync(h->d_rs_stage.p, 0, h->LY.total * sizeof(double), h->stream));
+        HIPCHK(hipMemsetAsync(h->d_rs_commit.p, 0, h->LY.total * sizeof(double), h->stream));
     }
     std::memcpy(h->s_fixed.p, pl.fixed_bits.data(), pl.fixed_bits.size() * sizeof(uint64_t));
     std::memcpy(h->s_brow_ptr.p, pl.brow_ptr.data(), pl.brow_ptr.size() * sizeof(int32_t));
     std::memcpy(h->s_brow_ent.p, pl.brow_ent.data(), pl.brow_ent.size() * sizeof(uint32_t));
+    return LH_OK;
+}
 
-    // ---- camera extrinsics (Sophus SE3 of Camera::pose_) and the initial pose tables ----
+// camera extrinsics (Sophus SE3 of Camera::pose_) and the initial pose tables into the staging
+struct ExtFlags {
+    int identity = 0, rot_identity = 0;   // bit c: camera c's extrinsic (its rotation) is exactly the identity
+};
+ExtFlags pose_tables(lh_handle* h, const lh_window* w) {
+    const int P = h->P, ncam = h->ncam;
     double* ext = h->s_ext.p;
-    int ext_identity = 0, ext_rot_identity = 0;
+    ExtFlags fl;
     for (int c = 0; c < ncam; ++c) {
         static const double I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
         const double* E = (w->n_cams > 0) ? w->cam_ext + 12 * c : I12;
@@ -714,8 +703,8 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
         e[4] = E[3]; e[5] = E[7]; e[6] = E[11];
         for (int i = 0; i < 9; ++i) e[7 + i] = Rq[i];
         if (q[0] == 1.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) {
-            ext_rot_identity |= 1 << c;
-            if (e[4] == 0.0 && e[5] == 0.0 && e[6] == 0.0) ext_identity |= 1 << c;
+            fl.rot_identity |= 1 << c;
+            if (e[4] == 0.0 && e[5] == 0.0 && e[6] == 0.0) fl.identity |= 1 << c;
         }
     }
     for (int p = 0; p < P; ++p) {
@@ -726,121 +715,94 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
                 pose_table(T, ext + LH_EXT * (size_t)c, h->s_ptab.p + ((size_t)s * P * ncam + (size_t)p * ncam + c) * LH_PT);
         }
     }
+    return fl;
+}
 
-    // ---- the sharded upload's envelope collective.  Word 0 carries the largest status of any rank (a rank
-    //      that failed earlier joins from upload_impl with its own), then -pf per pose: the union envelope.
-    //      Everything after it is decided on data identical on every rank; a rank-local failure after it
-    //      (allocations, the image initialisation, the copies) is shared by upload_impl's closing status
-    //      all-reduce. ----
-    if (sharded) {
-        std::vector<double> neg(1 + (size_t)P);
-        neg[0] = 0.0;
-        for (int p = 0; p < P; ++p) neg[1 + p] = -(double)pf[p];
-        h->upload_joined = true;
-        const int st_r = rank_max(h, neg.data(), 1 + P);
-        if (st_r != LH_OK) return st_r;
-        if (neg[0] > 0.0) return (int)neg[0];
-        for (int p = 0; p < P; ++p) pf[p] = (int)(-neg[1 + p]);
-        h->upload_tail = true;
-        // (test hook) this rank fails after the collective, as a failed allocation in the tail would
-        const char* fail_env = getenv("LH_TEST_FAIL_AFTER_ENVELOPE");
-        if (fail_env && atoi(fail_env) == h->opt.rank) return LH_E_HIP;
-    }
+// The sharded upload's envelope collective.  Word 0 carries the largest status of any rank (a rank
+// that failed earlier joins from upload_impl with its own), then -pf per pose: the union envelope.
+// Everything after it is decided on data identical on every rank; a rank-local failure after it
+// (allocations, the image initialisation, the copies) is shared by upload_impl's closing status
+// all-reduce.
+int envelope_collective(lh_handle* h, std::vector<int>& pf) {
+    if (!(h->host_comm || h->comm || h->p2p)) return LH_OK;
+    const int P = h->P;
+    std::vector<double> neg(1 + (size_t)P);
+    neg[0] = 0.0;
+    for (int p = 0; p < P; ++p) neg[1 + p] = -(double)pf[p];
+    h->upload_joined = true;
+    const int st_r = rank_max(h, neg.data(), 1 + P);
+    if (st_r != LH_OK) return st_r;
+    if (neg[0] > 0.0) return (int)neg[0];
+    for (int p = 0; p < P; ++p) pf[p] = (int)(-neg[1 + p]);
+    h->upload_tail = true;
+    // (test hook) this rank fails after the collective, as a failed allocation in the tail would
+    const char* fail_env = getenv("LH_TEST_FAIL_AFTER_ENVELOPE");
+    if (fail_env && atoi(fail_env) == h->opt.rank) return LH_E_HIP;
+    return LH_OK;
+}
 
-    // ---- the banded controller's eligibility (tile rows enter its window two steps before use) ----
-    std::vector<uint16_t> bunits;
-    if (band_possible) {
-        const int n = 6 * P, NE = (n + 15) & ~15, NT = NE / 16;
-        std::vector<int32_t> fcb(NT);
-        bool ok = true;
-        for (int I = 0; I < NT; ++I) {
-            int f = 1 << 20;
-            for (int r = 16 * I; r < 16 * I + 16; ++r) f = std::min(f, r < n ? 6 * pf[r / 6] : r);
-            fcb[I] = f >> 3;
-            if (I >= 8 && fcb[I] < 2 * I - 13) ok = false;   // a tile row must enter the window before it is used
-        }
-        if (ok) {
-            bunits.resize(16 * (size_t)kBandSteps);
-            const int order[LH_BAND_UNIT_WAVES] = LH_ORDER_BAND;
-            // the 11 unit waves when every step fits them (k_ctrl_b<false>), else with the loaders too
-            const int w11 = lh_ctrl_units(n, fcb.data(), order, 11, kBandSteps, bunits.data());
-            h->band_lu = w11 > 11;
-            if (h->band_lu)
-                ok = lh_ctrl_units(n, fcb.data(), order, LH_BAND_UNIT_WAVES, kBandSteps, bunits.data()) <= LH_BAND_UNIT_WAVES;
-        }
-        h->band = ok;
-        // k_ctrl_b's one-row-per-lane back substitution: block KB's L rows reach no column below KB - 56
-        bool narrow = ok && !getenv("LH_NO_NARROW");
-        for (int r = 0; r < n && narrow; ++r) narrow = 6 * pf[r / 6] >= (r & ~7) - 56;
-        h->band_narrow = narrow;
-    }
-    if (P > LH_PMAX_WIN && h->opt.linear_solver == LH_SOLVER_LDLT && !h->band) return LH_E_UNSUPPORTED;
-    // batches of evaluate-only rungs (every controller, one rank or sharded; LH_NO_BATCH=1: one rung
-    // per chain, the A/B switch; LH_BATCH_MAX caps the rungs per batch): per rung a per-edge rho0 and the chunk scalars
-    const bool dec1 = (P <= LH_PMAX || h->band) && h->opt.world_size == 1 && !h->comm;
-    int batch = (ladder > 1 && !getenv("LH_NO_BATCH")) ? ladder : 1;
-    if (const char* bm = getenv("LH_BATCH_MAX")) batch = std::max(1, std::min(batch, atoi(bm)));
-    HIPCHK(h->d_rho.ensure((size_t)batch * pl.n_slots));
-    HIPCHK(h->d_csc.ensure((size_t)batch * pl.n_chunks * 4));
-    if (h->band) {   // k_ctrl_b's L rows and ND blocks; L entries outside the envelope are never written: zero
-        const size_t NE = (size_t)((6 * P + 15) & ~15);
-        const size_t per = NE * 128 + (size_t)(6 * LH_PMAX_ANY / 8) * 64;   // one rung's (k_ctrl_b's layout)
-        HIPCHK(h->d_band.ensure((size_t)ladder * per));
-        HIPCHK(hipMemsetAsync(h->d_band.p, 0, (size_t)ladder * per * sizeof(double), h->stream));
-    } else if (P > LH_PMAX && h->opt.linear_solver == LH_SOLVER_LDLT) {   // k_ctrl_g's system, stride ceil32(6P); zeroed once
-        const size_t ng = (size_t)((6 * P + 31) & ~31);
-        h->lad_stride = ng * ng;   // one gA per ladder rung
-        const bool fresh = h->d_gA.n < (size_t)ladder * ng * ng;
-        HIPCHK(h->d_gA.ensure((size_t)ladder * ng * ng));
+int configure(lh_handle* h, const std::vector<int>& pf, const lh::Switches& sw) {
+    lh::SolveIn in;
+    in.P = h->P;
+    in.n_brow_ent = h->plan.brow_ent.size();
+    in.pf = pf.data();
+    in.linear_solver = h->opt.linear_solver;
+    in.max_trials = h->opt.max_trials;
+    in.world_size = h->opt.world_size;
+    in.rccl = h->comm != nullptr;
+    in.sw = sw;
+    return lh::solve_config(in, h->cfg);
+}
+
+// the buffers the configuration sizes, and what of them is cleared per window
+int controller_buffers(lh_handle* h) {
+    const lh::SolveConfig& c = h->cfg;
+    const lh::Plan& pl = h->plan;
+    // per batch rung a per-edge rho0 and the chunk scalars
+    HIPCHK(h->d_rho.ensure((size_t)c.batch * pl.n_slots));
+    HIPCHK(h->d_csc.ensure((size_t)c.batch * pl.n_chunks * 4));
+    if (c.kind == LH_CTRL_BAND) {   // k_ctrl_b's L rows and ND blocks; L entries outside the envelope are never written: zero
+        const size_t nb = (size_t)c.ladder * c.n_band;
+        HIPCHK(h->d_band.ensure(nb));
+        HIPCHK(hipMemsetAsync(h->d_band.p, 0, nb * sizeof(double), h->stream));
+    } else if (c.kind == LH_CTRL_PCG) {
+        HIPCHK(h->d_gA.ensure(c.n_gA));
+    } else if (c.kind == LH_CTRL_DENSE) {   // k_ctrl_g's systems and k_dense's S: zeroed once, when grown
+        const bool fresh = h->d_gA.n < c.n_gA;
+        HIPCHK(h->d_gA.ensure(c.n_gA));
         if (fresh) HIPCHK(hipMemsetAsync(h->d_gA.p, 0, h->d_gA.n * sizeof(double), h->stream));
-        // k_dense's dense symmetric S, double-buffered with the committed state
-        const bool fresh_s = h->d_gS.n < 2 * ng * ng;
-        HIPCHK(h->d_gS.ensure(2 * ng * ng));
+        const bool fresh_s = h->d_gS.n < c.n_gS;
+        HIPCHK(h->d_gS.ensure(c.n_gS));
         if (fresh_s) HIPCHK(hipMemsetAsync(h->d_gS.p, 0, h->d_gS.n * sizeof(double), h->stream));
     }
-
-    // ---- k_ctrl's work units: the envelope of S in natural pose order ----
-    if (P <= LH_PMAX) {
-        int32_t fcb[8];
-        for (int I = 0; I < 8; ++I) fcb[I] = 0;
-        const int n = 6 * P, NE = (n + 15) & ~15;
-        for (int I = 0; I < NE / 16; ++I) {
-            int f = 1 << 20;
-            for (int r = 16 * I; r < 16 * I + 16; ++r) f = std::min(f, r < n ? 6 * pf[r / 6] : r);
-            fcb[I] = f >> 3;
-        }
-        // the two-chain schedule (opt-in, LH_ND=1): fewer steps where the window splits into decoupled
-        // parts, but the separator's fill makes the early steps heavier; on C3 it measured slower than
-        // the one-chain schedule
-        h->nd.nsteps = 0;
-        const char* nd_env = getenv("LH_ND");
-        if (h->opt.linear_solver == LH_SOLVER_LDLT && nd_env && nd_env[0] == '1') lh_ctrl_nd_plan(P, pf.data(), h->nd);
-        if (h->nd.nsteps > 0) {
-            std::memcpy(h->s_units.p, h->nd.units, sizeof(h->nd.units));
-        } else {
-            const int order[15] = LH_ORDER_CTRL;
-            lh_ctrl_units(6 * P, fcb, order, 15, LH_NSTEP, h->s_units.p);
-        }
-    } else {
-        h->nd.nsteps = 0;
+    if (c.bimg) {   // entries no pair block writes stay zero: cleared per window
+        HIPCHK(h->d_img.ensure(c.n_img));
+        HIPCHK(hipMemsetAsync(h->d_img.p, 0, c.n_img * sizeof(double), h->stream));
     }
-
-    if (h->band) {
-        std::memcpy(h->s_bunits.p, bunits.data(), bunits.size() * sizeof(uint16_t));
-        int32_t* bb = h->s_bblk.p;
-        for (size_t i = 0; i < (size_t)P * 64; ++i) bb[i] = -1;
-        for (int b = 0; b < pl.npairs; ++b) {
-            const int p = pl.pair_list[2 * b], q = pl.pair_list[2 * b + 1];
-            if (q - p < 64) bb[p * 64 + (q - p)] = b;
-        }
+    if (c.img) {
+        HIPCHK(h->d_img.ensure(c.n_img));
+        HIPCHK(lh_launch_img_init(h->stream, h->d_img.p, 6 * h->P));
     }
+    return LH_OK;
+}
 
-    // ---- params ----
+// the controller's work units, and k_ctrl_b's pair -> block table, into the staging
+void stage_tables(lh_handle* h) {
+    const lh::SolveConfig& c = h->cfg;
+    if (c.kind == LH_CTRL_LDS) std::memcpy(h->s_units.p, c.units.data(), c.units.size() * sizeof(uint16_t));
+    if (c.kind == LH_CTRL_BAND) {
+        std::memcpy(h->s_bunits.p, c.units.data(), c.units.size() * sizeof(uint16_t));
+        lh::band_block_table(h->plan, h->s_bblk.p);
+    }
+}
+
+void set_params(lh_handle* h, const lh_window* w, const ExtFlags& ext) {
+    const lh::SolveConfig& c = h->cfg;
     lh_params& prm = h->prm;
-    prm.P = P;
-    prm.npairs = pl.npairs;
-    prm.n = 6 * P;
-    prm.ncam = ncam;
+    prm.P = h->P;
+    prm.npairs = h->plan.npairs;
+    prm.n = 6 * h->P;
+    prm.ncam = h->ncam;
     prm.max_iters = h->opt.max_iters;
     prm.max_trials = h->opt.max_trials;
     prm.strategy = h->opt.strategy;
@@ -848,8 +810,8 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
     prm.gate_mode = h->opt.gate_mode;
     prm.precision = h->opt.precision;
     prm.lambda_given = h->opt.lambda_init >= 0.0;
-    prm.ext_identity = ext_identity;
-    prm.ext_rot_identity = ext_rot_identity;
+    prm.ext_identity = ext.identity;
+    prm.ext_rot_identity = ext.rot_identity;
     prm.huber_delta = h->opt.huber_delta;
     prm.stop_dchi2 = h->opt.stop_dchi2;
     prm.tau = h->opt.tau;
@@ -858,58 +820,60 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
     prm.solver = h->opt.linear_solver;
     prm.pcg_tol = h->opt.pcg_tol;
     prm.pcg_max_it = h->opt.pcg_max_iters;
-    prm.no_evo = getenv("LH_NO_EVO") != nullptr;
-    prm.eval_first = getenv("LH_NO_EVAL_FIRST") == nullptr;
-    prm.dec_in_reduce = dec1 ? 1 : 0;
-    prm.batch = batch;
-    prm.n_chunks = (int32_t)pl.n_chunks;
-    prm.commit_in_reduce = h->band ? 1 : 0;
-    // every controller builds the ladder: with k_reduce's decision (one rank, k_ctrl and k_ctrl_b) its rungs read it
-    // from lh_ctrl; a controller that decides itself (the initial linearisation, sharded solves, k_ctrl_g, k_ctrl_p)
-    // publishes its workgroup 0's decision to its rungs (ladder_publish / ladder_wait)
-    prm.ladder = ladder;
-    prm.lad_stride = (int32_t)h->lad_stride;
-    // every factor builds the ladder (LH_LADDER_LAZY=1: only a factor after a rejection; the live configuration
-    // measured 7 582 against 7 251 it/s, the headline window unchanged, profiles/r06c_*)
-    prm.ladder_eager = getenv("LH_LADDER_LAZY") ? 0 : 1;
-    prm.band_narrow = h->band_narrow ? 1 : 0;
-    prm.band_lu = h->band_lu ? 1 : 0;
-    // k_reduce writes the band straight into k_ctrl_b's loader order (one rank; LH_NO_BIMG=1: the packed
-    // blocks and the loaders' block-index round trip, an A/B switch)
-    prm.bimg = (h->band && prm.dec_in_reduce && !getenv("LH_NO_BIMG")) ? 1 : 0;
-    if (prm.bimg) {   // entries no pair block writes stay zero: cleared per window
-        const size_t nbi = 2 * (size_t)((6 * P + 15) >> 4) * LH_BIMG_TR;
-        HIPCHK(h->d_img.ensure(nbi));
-        HIPCHK(hipMemsetAsync(h->d_img.p, 0, nbi * sizeof(double), h->stream));
-    }
-    // k_reduce hands k_ctrl the system in its LDS layout (one rank, P <= LH_PMAX, the one-chain LDL^T;
-    // LH_NO_IMG=1: the packed system and k_ctrl's scatter, an A/B switch)
-    prm.img = (prm.dec_in_reduce && P <= LH_PMAX && h->opt.linear_solver == LH_SOLVER_LDLT && h->nd.nsteps == 0 &&
-               !getenv("LH_NO_IMG")) ? 1 : 0;
-    if (prm.img) {
-        HIPCHK(h->d_img.ensure(2 * (size_t)LH_IMG_SZ));
-        HIPCHK(lh_launch_img_init(h->stream, h->d_img.p, 6 * P));
-    }
-    prm.nd_steps = h->nd.nsteps;
-    prm.nd_a = h->nd.a;
-    prm.nd_s = h->nd.s;
-    prm.nd_long_first = h->nd.long_first;
+    prm.no_evo = c.no_evo;
+    prm.eval_first = c.eval_first;
+    prm.dec_in_reduce = c.dec_in_reduce;
+    prm.batch = c.batch;
+    prm.n_chunks = (int32_t)h->plan.n_chunks;
+    prm.commit_in_reduce = c.commit_in_reduce;
+    prm.ladder = c.ladder;
+    prm.lad_stride = (int32_t)c.lad_stride;
+    prm.ladder_eager = c.ladder_eager;
+    prm.band_narrow = c.band_narrow ? 1 : 0;
+    prm.band_lu = c.band_lu ? 1 : 0;
+    prm.bimg = c.bimg;
+    prm.img = c.img;
+    prm.nd_steps = c.nd.nsteps;
+    prm.nd_a = c.nd.a;
+    prm.nd_s = c.nd.s;
+    prm.nd_long_first = c.nd.long_first;
     for (int i = 0; i < 4; ++i) prm.K[i] = w->K[i];
-    const double t1 = now_ms();
+}
 
-    // ---- the remaining copies ----
+// every per-window table in one copy, and the event the next upload waits for
+int send_arena(lh_handle* h, bool sync) {
     hipStream_t s = h->stream;
-    auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        if (!bytes) return hipSuccess;
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-    };
-    HIPCHK(up(h->d_arena.p, h->s_arena.p, h->arena_bytes));   // every per-window table in one copy
+    if (h->arena_bytes)
+        HIPCHK(hipMemcpyAsync(h->d_arena.p, h->s_arena.p, h->arena_bytes, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(h->ev_staging, s));
     h->staging_pending = true;
     if (sync) {
         HIPCHK(spin_wait(h->ev_staging));
         h->staging_pending = false;
     }
+    return LH_OK;
+}
+
+int upload_body(lh_handle* h, const lh_window* w, bool sync) {
+    const double t0 = now_ms();
+    h->uploaded = false;
+    const lh::Switches sw = lh::read_switches();
+    STAGE(wait_staging(h));
+    STAGE(send_landmarks(h, w));
+    STAGE(plan_window(h, w));
+    std::vector<int> pf = lh::plan_envelope(h->plan);   // this rank's; the collective below unites the ranks'
+    STAGE(rank_local_limits(h));
+    STAGE(bind_arena(h, lh::band_possible(h->plan.P, h->opt.linear_solver, sw)));
+    STAGE(window_buffers(h, lh::ladder_rungs(h->opt.max_trials, sw)));
+    STAGE(fill_staging(h, w, sw));
+    const ExtFlags ext = pose_tables(h, w);
+    STAGE(envelope_collective(h, pf));
+    STAGE(configure(h, pf, sw));
+    STAGE(controller_buffers(h));
+    stage_tables(h);
+    set_params(h, w, ext);
+    const double t1 = now_ms();
+    STAGE(send_arena(h, sync));
     h->last_prep_ms = t1 - t0;
     h->last_upload_ms = now_ms() - t0;
     h->uploaded = true;
@@ -969,9 +933,8 @@ int host_exchange(lh_handle* h, int mode) {
 }
 
 lh_band_args band_args(lh_handle* h) {
-    if (!h->band) return lh_band_args{nullptr, nullptr, nullptr, nullptr};
-    const size_t NE = (size_t)((6 * h->P + 15) & ~15);
-    return lh_band_args{h->d_bblk.p, h->d_bunits.p, h->d_band.p, h->d_band.p + NE * 128};
+    if (h->cfg.kind != LH_CTRL_BAND) return lh_band_args{nullptr, nullptr, nullptr, nullptr};
+    return lh_band_args{h->d_bblk.p, h->d_bunits.p, h->d_band.p, h->d_band.p + lh::band_scratch(h->P).nd_off};
 }
 
 // P2P: the exchange of chain `seq` (lh_launch_p2p; tags carry the solve count, so no stale tag ever matches)
@@ -1018,11 +981,11 @@ int enqueue_trial(lh_handle* h, int mode, bool* stopped) {
     }
     {
         Prof pr(h, KC_CTRL);
-        if (h->P > LH_PMAX && h->prm.solver == LH_SOLVER_LDLT && !h->band)
+        if (h->cfg.kind == LH_CTRL_DENSE)
             HIPCHK(lh_launch_dense(s, h->d_rs_stage.p, h->d_pair_pq.p, h->d_ctrl.p, h->d_gS.p, h->P));
         HIPCHK(lh_launch_ctrl(s, h->d_ctrl.p, h->d_rs_commit.p, h->d_rs_stage.p, h->d_maxd.p, h->d_rsmap.p, h->d_pair_pq.p,
                               h->d_dxp.p, h->prm, mode, h->d_done, h->cur_trial, h->d_gA.p, h->d_gS.p, h->d_brow_ptr.p,
-                              h->d_brow_ent.p, h->d_units.p, band_args(h), h->d_img.p));
+                              h->d_brow_ent.p, h->d_units.p, band_args(h), h->d_img.p, h->cfg.kind));
         DBGSYNC("k_ctrl");
     }
     return LH_OK;
@@ -1946,7 +1909,7 @@ int lh_debug_chains(lh_handle* h, int* chains) {
 int lh_debug_ladder(lh_handle* h, int* rungs, int* skipped) {
     if (!h || !rungs || !skipped) return LH_E_BADARG;
     if (!h->uploaded) return LH_E_STATE;
-    *rungs = h->prm.ladder;
+    *rungs = h->cfg.ladder;
     *skipped = h->last_lskips;
     return LH_OK;
 }
@@ -1954,7 +1917,7 @@ int lh_debug_ladder(lh_handle* h, int* rungs, int* skipped) {
 int lh_debug_batch(lh_handle* h, int* batch_max, int* batches, int* retrials) {
     if (!h || !batch_max || !batches) return LH_E_BADARG;
     if (!h->uploaded) return LH_E_STATE;
-    *batch_max = h->prm.batch;
+    *batch_max = h->cfg.batch;
     *batches = h->last_batches;
     if (retrials) { retrials[0] = h->last_retrials[0]; retrials[1] = h->last_retrials[1]; }
     return LH_OK;
@@ -1963,9 +1926,8 @@ int lh_debug_batch(lh_handle* h, int* batch_max, int* batches, int* retrials) {
 int lh_debug_controller(lh_handle* h, int* which) {
     if (!h || !which) return LH_E_BADARG;
     if (!h->uploaded) return LH_E_STATE;
-    *which = h->P <= LH_PMAX ? 0 : h->band ? 3 : h->prm.solver == LH_SOLVER_PCG ? 2 : 1;
-    if (h->band_narrow) *which |= 1 << 8;   // k_ctrl_b's one-row-per-lane back substitution
-    if (h->band_lu) *which |= 1 << 9;       // k_ctrl_b's stream loaders take units (k_ctrl_b<true>)
+    // lh_ctrl_kind | bit 8: k_ctrl_b's one-row-per-lane back substitution | bit 9: its stream loaders take units
+    *which = h->cfg.debug_word();
     return LH_OK;
 }
 

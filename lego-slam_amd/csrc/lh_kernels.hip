@@ -5359,9 +5359,9 @@ hipError_t lh_launch_img_init(hipStream_t st, double* img, int n) {
     return hipGetLastError();
 }
 
+// k_ctrl_g's dense S (the caller launches it exactly for LH_CTRL_DENSE windows)
 hipError_t lh_launch_dense(hipStream_t st, const double* rs_stage, const uint16_t* pair_pq, const lh_ctrl* ctrl,
                            double* gS, int P) {
-    if (P <= LH_PMAX) return hipSuccess;
     const int NG = (6 * P + GNB - 1) & ~(GNB - 1);
     hipLaunchKernelGGL(k_dense, dim3(P * (P + 1) / 2), dim3(64), 0, st, rs_stage, pair_pq, ctrl, gS, P, NG);
     return hipGetLastError();
@@ -5370,24 +5370,26 @@ hipError_t lh_launch_dense(hipStream_t st, const double* rs_stage, const uint16_
 hipError_t lh_launch_ctrl(hipStream_t st, lh_ctrl* ctrl, double* rs_commit, const double* rs_stage, const double* maxd,
                           const uint32_t* rsmap, const uint16_t* pair_pq, double* dxp, lh_params prm, int mode,
                           int* host_done, int seq, double* gA, const double* gS, const int32_t* brow_ptr,
-                          const uint32_t* brow_ent, const uint16_t* units, lh_band_args band, double* img) {
+                          const uint32_t* brow_ent, const uint16_t* units, lh_band_args band, double* img, int kind) {
     const dim3 gl(prm.ladder > 1 ? prm.ladder : 1);   // one workgroup per lambda-ladder rung
-    if (prm.P > LH_PMAX && prm.solver == 0 && band.bblk)
-    {
+    switch (kind) {   // lh_ctrl_kind, the window's solve configuration (lh_plan.h)
+    case LH_CTRL_BAND:
         if (prm.band_lu)
             hipLaunchKernelGGL(k_ctrl_b<true>, gl, dim3(CT), 0, st, ctrl, rs_commit, rs_stage, maxd, band.bblk,
                                band.units, band.Lg, band.NDg, dxp, prm, mode, (volatile int*)host_done, seq, img);
         else
             hipLaunchKernelGGL(k_ctrl_b<false>, gl, dim3(CT), 0, st, ctrl, rs_commit, rs_stage, maxd, band.bblk,
                                band.units, band.Lg, band.NDg, dxp, prm, mode, (volatile int*)host_done, seq, img);
-    }
-    else if (prm.P > LH_PMAX && prm.solver == 1)
+        break;
+    case LH_CTRL_PCG:
         hipLaunchKernelGGL(k_ctrl_p, gl, dim3(CT), 0, st, ctrl, rs_commit, rs_stage, maxd, brow_ptr, brow_ent,
                            dxp, prm, mode, (volatile int*)host_done, seq, gA);   // gA: the PCG's row scratch
-    else if (prm.P > LH_PMAX)
+        break;
+    case LH_CTRL_DENSE:
         hipLaunchKernelGGL(k_ctrl_g, gl, dim3(GT), 0, st, ctrl, rs_commit, rs_stage, maxd, rsmap,
                            dxp, prm, mode, (volatile int*)host_done, seq, gA, gS);
-    else {
+        break;
+    case LH_CTRL_LDS: {
         // k_ctrl deciding itself: one more workgroup, the decider of batch chains (ctrl_batch_decider)
         const dim3 gk(gl.x + (prm.dec_in_reduce ? 0 : 1));
         if (prm.solver == 1)
@@ -5399,6 +5401,10 @@ hipError_t lh_launch_ctrl(hipStream_t st, lh_ctrl* ctrl, double* rs_commit, cons
         else
             hipLaunchKernelGGL((k_ctrl<0, false>), gk, dim3(CT), 0, st, ctrl, rs_commit, rs_stage, maxd, pair_pq,
                                units, dxp, prm, mode, (volatile int*)host_done, seq, img);
+        break;
+    }
+    default:
+        return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

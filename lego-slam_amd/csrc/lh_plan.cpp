@@ -714,4 +714,185 @@ int plan_fill(const lh_window* w, const Plan& pl, const PlanOut& out, Pool* pool
     return LH_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The solve configuration
+// ---------------------------------------------------------------------------------------------
+Switches read_switches() {
+    Switches s;
+    s.no_band = getenv("LH_NO_BAND") != nullptr;
+    s.no_ladder = getenv("LH_NO_LADDER") != nullptr;
+    s.no_red_skip = getenv("LH_NO_RED_SKIP") != nullptr;
+    s.no_narrow = getenv("LH_NO_NARROW") != nullptr;
+    s.no_batch = getenv("LH_NO_BATCH") != nullptr;
+    if (const char* bm = getenv("LH_BATCH_MAX")) s.batch_max = atoi(bm);
+    const char* nd = getenv("LH_ND");
+    s.nd = nd && nd[0] == '1';
+    s.no_evo = getenv("LH_NO_EVO") != nullptr;
+    s.no_eval_first = getenv("LH_NO_EVAL_FIRST") != nullptr;
+    s.ladder_lazy = getenv("LH_LADDER_LAZY") != nullptr;
+    s.no_bimg = getenv("LH_NO_BIMG") != nullptr;
+    s.no_img = getenv("LH_NO_IMG") != nullptr;
+    return s;
+}
+
+std::vector<int> plan_envelope(const Plan& pl) {
+    std::vector<int> pf(pl.P);
+    for (int p = 0; p < pl.P; ++p) pf[p] = p;
+    for (size_t c = 0; c < pl.chunk_mask.size(); ++c) {
+        const uint64_t m = pl.chunk_mask[c];
+        if (!m) continue;
+        const int lo = pl.chunk_base[c] + __builtin_ctzll(m);
+        for (uint64_t b = m; b; b &= b - 1) {
+            const int p = pl.chunk_base[c] + __builtin_ctzll(b);
+            pf[p] = std::min(pf[p], lo);
+        }
+    }
+    return pf;
+}
+
+namespace {
+// lh_ctrl_units' tile_fcb of a P-pose window: 16-row tile row I first reaches the 8-column block of its
+// rows' lowest envelope start (a padding row holds its diagonal alone); fcb[ceil16(6P) / 16]
+void tile_fcb(int P, const int* pf, int32_t* fcb) {
+    const int n = 6 * P, NT = ((n + 15) & ~15) / 16;
+    for (int I = 0; I < NT; ++I) {
+        int f = 1 << 20;
+        for (int r = 16 * I; r < 16 * I + 16; ++r) f = std::min(f, r < n ? 6 * pf[r / 6] : r);
+        fcb[I] = f >> 3;
+    }
+}
+}  // namespace
+
+int band_units(int n, const int32_t* fcb, uint16_t* units, bool* lu) {
+    const int order[LH_BAND_UNIT_WAVES] = LH_ORDER_BAND;
+    int worst = lh_ctrl_units(n, fcb, order, 11, kBandSteps, units);
+    *lu = worst > 11;
+    if (*lu) worst = lh_ctrl_units(n, fcb, order, LH_BAND_UNIT_WAVES, kBandSteps, units);
+    return worst;
+}
+
+// past LH_PMAX poses: LDL^T by k_ctrl_b when the reduced system is banded in natural pose order (any P
+// up to LH_PMAX_ANY), else by k_ctrl_g (dense, up to LH_PMAX_WIN poses); PCG by k_ctrl_p (block-sparse,
+// up to LH_PMAX_ANY)
+bool band_possible(int P, int linear_solver, const Switches& sw) {
+    return P > LH_PMAX && linear_solver == LH_SOLVER_LDLT && !sw.no_band;
+}
+
+// the lambda ladder's rungs, one controller workgroup each: one pending step per rung,
+// and per rung the controller's global scratch
+int ladder_rungs(int max_trials, const Switches& sw) {
+    return !sw.no_ladder ? std::max(1, std::min(max_trials, LH_LAD)) : 1;
+}
+
+int solve_config(const SolveIn& in, SolveConfig& c) {
+    c = SolveConfig{};
+    const Switches& sw = in.sw;
+    const int P = in.P, n = 6 * P;
+    const bool ldlt = in.linear_solver == LH_SOLVER_LDLT;
+
+    // ---- the banded controller's eligibility (tile rows enter its window two steps before use) ----
+    bool band = false;
+    if (band_possible(P, in.linear_solver, sw)) {
+        const int NT = ((n + 15) & ~15) / 16;
+        std::vector<int32_t> fcb(NT);
+        tile_fcb(P, in.pf, fcb.data());
+        bool ok = true;
+        for (int I = 8; I < NT; ++I)
+            if (fcb[I] < 2 * I - 13) ok = false;   // a tile row must enter the window before it is used
+        if (ok) {   // (band_lu stands even where the loaders' waves do not suffice either)
+            c.units.resize(16 * (size_t)kBandSteps);
+            ok = band_units(n, fcb.data(), c.units.data(), &c.band_lu) <= LH_BAND_UNIT_WAVES;
+        }
+        band = ok;
+        if (!band) c.units.clear();
+        // k_ctrl_b's one-row-per-lane back substitution: block KB's L rows reach no column below KB - 56
+        bool narrow = ok && !sw.no_narrow;
+        for (int r = 0; r < n && narrow; ++r) narrow = 6 * in.pf[r / 6] >= (r & ~7) - 56;
+        c.band_narrow = narrow;
+    }
+    if (P > LH_PMAX_WIN && ldlt && !band) return LH_E_UNSUPPORTED;
+    c.kind = P <= LH_PMAX ? LH_CTRL_LDS : band ? LH_CTRL_BAND : in.linear_solver == LH_SOLVER_PCG ? LH_CTRL_PCG : LH_CTRL_DENSE;
+
+    // ---- the ladder, and batches of evaluate-only rungs (every controller, one rank or
+    //      sharded): per rung a per-edge rho0 and the chunk scalars ----
+    c.ladder = ladder_rungs(in.max_trials, sw);
+    c.batch = (c.ladder > 1 && !sw.no_batch) ? c.ladder : 1;
+    c.batch = std::max(1, std::min(c.batch, sw.batch_max));
+    // every factor builds the ladder (LH_LADDER_LAZY=1: only a factor after a rejection; the live configuration
+    // measured 7 582 against 7 251 it/s, the headline window unchanged, profiles/r06c_*)
+    c.ladder_eager = sw.ladder_lazy ? 0 : 1;
+    c.no_evo = sw.no_evo ? 1 : 0;
+    c.eval_first = sw.no_eval_first ? 0 : 1;
+
+    // ---- the controller's global scratch ----
+    if (c.kind == LH_CTRL_BAND) {
+        c.n_band = band_scratch(P).per_rung;
+    } else if (c.kind == LH_CTRL_PCG) {   // k_ctrl_p's row-contiguous copy of S (36 per block-row entry)
+        c.lad_stride = in.n_brow_ent * 36;
+        c.n_gA = (size_t)c.ladder * c.lad_stride;
+    } else if (c.kind == LH_CTRL_DENSE) {   // k_ctrl_g's system, stride ceil32(6P), one per ladder rung
+        const size_t ng = (size_t)((n + 31) & ~31);
+        c.lad_stride = ng * ng;
+        c.n_gA = (size_t)c.ladder * ng * ng;
+        c.n_gS = 2 * ng * ng;   // k_dense's dense symmetric S, double-buffered with the committed state
+    }
+
+    // ---- k_ctrl's work units: the envelope of S in natural pose order ----
+    if (c.kind == LH_CTRL_LDS) {
+        int32_t fcb[LH_NSTEP / 2] = {0};
+        tile_fcb(P, in.pf, fcb);
+        // the two-chain schedule (opt-in, LH_ND=1): fewer steps where the window splits into decoupled
+        // parts, but the separator's fill makes the early steps heavier; on C3 it measured slower than
+        // the one-chain schedule
+        if (ldlt && sw.nd) lh_ctrl_nd_plan(P, in.pf, c.nd);
+        c.units.resize(16 * LH_NSTEP);
+        if (c.nd.nsteps > 0) {
+            std::memcpy(c.units.data(), c.nd.units, sizeof(c.nd.units));
+        } else {
+            const int order[15] = LH_ORDER_CTRL;
+            lh_ctrl_units(n, fcb, order, 15, LH_NSTEP, c.units.data());
+        }
+    }
+
+    // ---- who decides, and in which layout k_reduce hands the system over ----
+    // every controller builds the ladder: with k_reduce's decision (one rank, k_ctrl and k_ctrl_b) its rungs read it
+    // from lh_ctrl; a controller that decides itself (the initial linearisation, sharded solves, k_ctrl_g, k_ctrl_p)
+    // publishes its workgroup 0's decision to its rungs (ladder_publish / ladder_wait)
+    const bool dec1 = (P <= LH_PMAX || band) && in.world_size == 1 && !in.rccl;
+    c.dec_in_reduce = dec1 ? 1 : 0;
+    c.commit_in_reduce = band ? 1 : 0;
+    // k_reduce writes the band straight into k_ctrl_b's loader order (one rank; LH_NO_BIMG=1: the packed
+    // blocks and the loaders' block-index round trip); entries no pair block writes stay zero
+    c.bimg = (band && dec1 && !sw.no_bimg) ? 1 : 0;
+    // k_reduce hands k_ctrl the system in its LDS layout (one rank, P <= LH_PMAX, the one-chain LDL^T;
+    // LH_NO_IMG=1: the packed system and k_ctrl's scatter)
+    c.img = (dec1 && P <= LH_PMAX && ldlt && c.nd.nsteps == 0 && !sw.no_img) ? 1 : 0;
+    if (c.bimg) c.n_img = 2 * (size_t)((n + 15) >> 4) * LH_BIMG_TR;
+    if (c.img) c.n_img = 2 * (size_t)LH_IMG_SZ;
+    return LH_OK;
+}
+
+bool reduce_skip(int world_size, const Switches& sw) { return world_size == 1 && !sw.no_red_skip; }
+
+int reduce_table(const Plan& pl, bool skip, uint32_t* rt) {
+    int k = 0;
+    for (int b = 0; b < pl.npairs; ++b) {
+        const uint32_t ib = pl.pair_ptr[b], ie = pl.pair_ptr[b + 1];
+        if (skip && ib == ie) continue;
+        rt[4 * k] = (uint32_t)b; rt[4 * k + 1] = ib; rt[4 * k + 2] = ie;
+        rt[4 * k + 3] = (uint32_t)pl.pair_list[2 * b] | ((uint32_t)pl.pair_list[2 * b + 1] << 16);
+        ++k;
+    }
+    rt[4 * k] = (uint32_t)pl.npairs; rt[4 * k + 1] = 0; rt[4 * k + 2] = 0; rt[4 * k + 3] = 0;
+    return k;
+}
+
+void band_block_table(const Plan& pl, int32_t* bb) {
+    for (size_t i = 0; i < (size_t)pl.P * 64; ++i) bb[i] = -1;
+    for (int b = 0; b < pl.npairs; ++b) {
+        const int p = pl.pair_list[2 * b], q = pl.pair_list[2 * b + 1];
+        if (q - p < 64) bb[p * 64 + (q - p)] = b;
+    }
+}
+
 }  // namespace lh

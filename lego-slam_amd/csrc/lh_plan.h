@@ -123,4 +123,94 @@ using SlotsReady = void (*)(void* user, int64_t slot_begin, int64_t slot_end);
 int plan_fill(const lh_window* w, const Plan& pl, const PlanOut& out, Pool* pool, SlotsReady on_slots = nullptr,
               void* user = nullptr, int batches = 1);
 
+// ---------------------------------------------------------------------------------------------
+// A window's solve configuration: which controller runs it, with which tables and
+// scratch sizes.  Pure functions of the plan, the handle's options and the environment switches;
+// lh_host.cpp allocates, fills and launches from what they return and decides nothing itself.
+// ---------------------------------------------------------------------------------------------
+
+// The environment switches of the solve configuration (A/B hooks of the bitwise tests and bench.py).
+// Read once per upload: a caller sets a variable and then uploads through a new solver.
+struct Switches {
+    bool no_band = false;         // LH_NO_BAND: past LH_PMAX poses LDL^T never runs banded (k_ctrl_g, up to LH_PMAX_WIN)
+    bool no_ladder = false;       // LH_NO_LADDER: one lambda-ladder rung
+    bool no_red_skip = false;     // LH_NO_RED_SKIP: k_reduce keeps the blocks of pose pairs no chunk couples
+    bool no_narrow = false;       // LH_NO_NARROW: k_ctrl_b's two-rows-per-lane back substitution on every window
+    bool no_batch = false;        // LH_NO_BATCH: one evaluate-only rung per chain
+    int batch_max = INT32_MAX;    // LH_BATCH_MAX=m: at most m (at least 1) rungs per batch
+    bool nd = false;              // LH_ND=1: k_ctrl's two-chain schedule where the window splits (LDL^T)
+    bool no_evo = false;          // LH_NO_EVO: every trial linearises in full
+    bool no_eval_first = false;   // LH_NO_EVAL_FIRST: a trial after a rejection is linearised, not only evaluated
+    bool ladder_lazy = false;     // LH_LADDER_LAZY: only a factor after a rejection builds the ladder
+    bool no_bimg = false;         // LH_NO_BIMG: k_ctrl_b's loaders read the packed blocks, not k_reduce's band image
+    bool no_img = false;          // LH_NO_IMG: k_ctrl scatters the packed system, not k_reduce's LDS image
+};
+Switches read_switches();
+
+// pf[p]: pose p's first coupled pose, the lowest pose of any chunk window holding p (a chunk writes a
+// block for every pair of its window): the envelope of S in natural pose order.  A sharded solve
+// factors the sum of every rank's blocks, so it unites the ranks' envelopes before solve_config.
+std::vector<int> plan_envelope(const Plan& pl);
+
+constexpr int kBandSteps = 6 * LH_PMAX_ANY / 8;   // k_ctrl_b's steps at most (its unit table's row length)
+
+// k_ctrl_b's unit table [16][kBandSteps] for an n-row system (lh_ctrl_units): the 11 unit waves when
+// every step fits them (*lu false, k_ctrl_b<false>), else the stream loaders take units too.  Returns
+// the most units a step needed (more than LH_BAND_UNIT_WAVES: the window cannot run banded).
+int band_units(int n, const int32_t* fcb, uint16_t* units, bool* lu);
+
+// k_ctrl_b's global scratch per ladder rung, in doubles: the L rows [ceil16(6P)][128], then ND per
+// block [kBandSteps][64]
+struct BandScratch {
+    size_t nd_off, per_rung;
+};
+inline BandScratch band_scratch(int P) {
+    const size_t NE = (size_t)((6 * P + 15) & ~15);
+    return {NE * 128, NE * 128 + (size_t)kBandSteps * 64};
+}
+
+// What is needed before a sharded upload's envelope collective, to size what every rank allocates
+// alike: may the window run banded at all (the arena reserves k_ctrl_b's tables), and the ladder's rungs.
+bool band_possible(int P, int linear_solver, const Switches& sw);
+int ladder_rungs(int max_trials, const Switches& sw);
+
+struct SolveIn {
+    int P = 0;
+    size_t n_brow_ent = 0;        // Plan::brow_ent.size()
+    const int* pf = nullptr;      // [P] plan_envelope, united over the ranks
+    int linear_solver = LH_SOLVER_LDLT, max_trials = 1, world_size = 1;
+    bool rccl = false;            // the trials' exchange is an RCCL all-reduce
+    Switches sw;
+};
+
+struct SolveConfig {
+    int kind = LH_CTRL_LDS;       // lh_ctrl_kind: the controller kernel
+    bool band_narrow = false;     // k_ctrl_b: every row's envelope starts within 56 rows of its 8-row block
+    bool band_lu = false;         // k_ctrl_b: some step needs the stream loaders as unit waves too
+    int ladder = 1, batch = 1;    // lambda-ladder rungs; evaluate-only rungs per batch
+    int ladder_eager = 1, no_evo = 0, eval_first = 1;   // lh_params fields that are switches alone
+    int dec_in_reduce = 0, commit_in_reduce = 0, img = 0, bimg = 0;   // lh_params fields of the same names
+    lh_ctrl_nd nd{};              // k_ctrl's two-chain schedule (nd.nsteps 0: the one-chain one)
+    size_t lad_stride = 0;        // doubles of d_gA per ladder rung (k_ctrl_g, k_ctrl_p)
+    size_t n_band = 0;            // doubles of d_band per ladder rung (k_ctrl_b: band_scratch)
+    size_t n_gA = 0, n_gS = 0;    // doubles of d_gA (every rung) and d_gS (k_ctrl_g, k_ctrl_p)
+    size_t n_img = 0;             // doubles of d_img (img: k_ctrl's two LDS images; bimg: k_ctrl_b's two band images)
+    std::vector<uint16_t> units;  // the controller's work units: k_ctrl's [16][LH_NSTEP], k_ctrl_b's [16][kBandSteps]
+    // lh_debug_controller's word
+    int debug_word() const { return kind | (band_narrow ? 1 << 8 : 0) | (band_lu ? 1 << 9 : 0); }
+};
+// LH_OK, or LH_E_UNSUPPORTED: LDL^T past LH_PMAX_WIN poses on a window that cannot run banded
+int solve_config(const SolveIn& in, SolveConfig& out);
+
+// k_reduce's blocks, one per pose pair that some chunk's rows reach ({block, first row, end row, p | q << 16}),
+// then the scalar block's sentinel, into out[4 (npairs + 1)].  One rank skips the pairs no chunk couples:
+// their blocks of S are zero for the whole window (the caller clears the reduced-system buffers per
+// window).  A sharded solve keeps every pair: a rank's empty pair still has to write its zero
+// contribution over last trial's all-reduced sum.  Returns the pair blocks listed.
+bool reduce_skip(int world_size, const Switches& sw);
+int reduce_table(const Plan& pl, bool skip, uint32_t* out);
+
+// k_ctrl_b's pair -> block table: bblk[p * 64 + d] is the block of pose pair (p, p + d), -1 if absent
+void band_block_table(const Plan& pl, int32_t* bblk);
+
 }  // namespace lh

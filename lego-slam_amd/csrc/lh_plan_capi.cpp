@@ -108,12 +108,53 @@ extern "C" {
 // -> k_ctrl_b's (15 unit waves, the stream loaders last, 6 LH_PMAX_ANY / 8 steps).  Returns the most units a step needed.
 int lhp_ctrl_units(int n, const int32_t* fcb, int band, uint16_t* units) {
     if (band) {
-        const int order[LH_BAND_UNIT_WAVES] = LH_ORDER_BAND;   // as lh_host.cpp: the 11 unit waves, else the loaders too
-        const int w = lh_ctrl_units(n, fcb, order, 11, 6 * LH_PMAX_ANY / 8, units);
-        return w <= 11 ? w : lh_ctrl_units(n, fcb, order, LH_BAND_UNIT_WAVES, 6 * LH_PMAX_ANY / 8, units);
+        bool lu;
+        return lh::band_units(n, fcb, units, &lu);
     }
     const int order[15] = LH_ORDER_CTRL;
     return lh_ctrl_units(n, fcb, order, 15, LH_NSTEP, units);
+}
+
+// The solve configuration lh_upload decides for window `w` on a handle with these options (window ->
+// plan_structure -> plan_envelope -> solve_config; one rank's envelope; the switches from the environment,
+// as an upload reads them).  out8 = {lh_debug_controller's word, ladder, batch, dec_in_reduce,
+// commit_in_reduce, img, bimg, nd_steps}; pf (optional) [n_poses]: the envelope.  Returns the lh_status.
+int lhp_solve_config(const lh_window* w, int linear_solver, int max_trials, int world_size, int rccl, int32_t* out8,
+                     int32_t* pf) {
+    lh::Plan pl;
+    lh::PlanCfg cfg;
+    cfg.rank_invariant_pairs = world_size > 1;
+    int st = lh::plan_structure(w, cfg, world_size > 1, pl, nullptr);
+    if (st != LH_OK) return st;
+    const std::vector<int> env = lh::plan_envelope(pl);
+    if (pf) std::copy(env.begin(), env.end(), pf);
+    lh::SolveIn in;
+    in.P = pl.P;
+    in.n_brow_ent = pl.brow_ent.size();
+    in.pf = env.data();
+    in.linear_solver = linear_solver;
+    in.max_trials = max_trials;
+    in.world_size = world_size;
+    in.rccl = rccl != 0;
+    in.sw = lh::read_switches();
+    lh::SolveConfig c;
+    st = lh::solve_config(in, c);
+    if (st != LH_OK) return st;
+    const int32_t v[8] = {c.debug_word(), c.ladder, c.batch, c.dec_in_reduce, c.commit_in_reduce, c.img, c.bimg, c.nd.nsteps};
+    std::memcpy(out8, v, sizeof(v));
+    return LH_OK;
+}
+
+// k_reduce's block table of window `w` (reduce_table; the skip rule from world_size and the environment):
+// table [4 (npairs + 1)], *n_blocks the pair blocks listed.  Returns the lh_status.
+int lhp_reduce_table(const lh_window* w, int world_size, uint32_t* table, int32_t* n_blocks) {
+    lh::Plan pl;
+    lh::PlanCfg cfg;
+    cfg.rank_invariant_pairs = world_size > 1;
+    const int st = lh::plan_structure(w, cfg, world_size > 1, pl, nullptr);
+    if (st != LH_OK) return st;
+    *n_blocks = lh::reduce_table(pl, lh::reduce_skip(world_size, lh::read_switches()), table);
+    return LH_OK;
 }
 
 // k_ctrl's two-chain schedule (lh_ctrl_nd_plan) for tests: info = {nsteps, a, s, long_first}, units

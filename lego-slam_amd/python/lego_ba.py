@@ -602,6 +602,8 @@ def _pl():
         lib.lhp_pool_stress.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.lhp_ctrl_units.argtypes = [C.c_int, vp, C.c_int, vp]
         lib.lhp_ctrl_nd.argtypes = [C.c_int, vp, vp, vp, vp]
+        lib.lhp_solve_config.argtypes = [C.POINTER(LhWindow), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+        lib.lhp_reduce_table.argtypes = [C.POINTER(LhWindow), C.c_int, vp, vp]
         lib.lhp_pool_stress.restype = C.c_int64
         _planlib = lib
     return _planlib
@@ -649,6 +651,37 @@ def ctrl_nd(pf):
     _pl().lhp_ctrl_nd(int(P), _ptr(f), _ptr(info), _ptr(u), _ptr(pos))
     return {"nsteps": int(info[0]), "a": int(info[1]), "s": int(info[2]), "long_first": int(info[3]),
             "units": u.reshape(16, 16), "pos": pos[:P].astype(np.int64)}
+
+
+def solve_config(w, linear_solver=LH_SOLVER_LDLT, max_trials=10, world_size=1, rccl=False):
+    """The solve configuration an upload of window `w` decides (lh_plan.h solve_config) on a handle with these
+    options, the switches read from the environment as an upload reads them: dict(controller, band_narrow,
+    band_loader_units, ladder, batch, dec_in_reduce, commit_in_reduce, img, bimg, nd_steps, pf: the envelope).
+    Raises LhError(LH_E_UNSUPPORTED) for a window the solver refuses there."""
+    ref = _WindowRef(w)
+    v = np.zeros(8, np.int32)
+    pf = np.zeros(max(int(ref.s.n_poses), 1), np.int32)
+    _check(_pl().lhp_solve_config(C.byref(ref.s), int(linear_solver), int(max_trials), int(world_size), int(bool(rccl)),
+                                  _ptr(v), _ptr(pf)), "lhp_solve_config")
+    word = int(v[0])
+    out = dict(zip(("ladder", "batch", "dec_in_reduce", "commit_in_reduce", "img", "bimg", "nd_steps"),
+                   (int(x) for x in v[1:])))
+    out.update(controller=("k_ctrl", "k_ctrl_g", "k_ctrl_p", "k_ctrl_b")[word & 0xff], band_narrow=bool(word >> 8 & 1),
+               band_loader_units=bool(word >> 9 & 1), pf=pf[:int(ref.s.n_poses)])
+    return out
+
+
+def reduce_table(w, world_size=1):
+    """k_reduce's block table for window `w` (lh_plan.h reduce_table; the skip rule from world_size and the
+    environment): (rows [n_blocks + 1][4] of {block, first row, end row, p | q << 16}, the sentinel last;
+    npairs; pair_ptr)."""
+    pw = plan_window(w, rank_invariant=world_size > 1)
+    npairs = len(pw["pair_ptr"]) - 1
+    ref = _WindowRef(w)
+    tab = np.zeros(4 * (npairs + 1), np.uint32)
+    n = np.zeros(1, np.int32)
+    _check(_pl().lhp_reduce_table(C.byref(ref.s), int(world_size), _ptr(tab), _ptr(n)), "lhp_reduce_table")
+    return tab.reshape(-1, 4)[:int(n[0]) + 1], npairs, pw["pair_ptr"]
 
 
 def pool_stress(threads, runs, n):

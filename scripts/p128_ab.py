@@ -8,9 +8,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "lego-slam_amd", "python")]
 import numpy as np  # noqa: E402
 import lego_ba      # noqa: E402
-from test_pcg import _many_pose_window  # noqa: E402
+from windows import stable_window  # noqa: E402
 
-w = _many_pose_window(128, 50000, 3)
+w = stable_window(128, 50000, 3)
 for lib in [None] + os.environ.get("LIB_OLD", "").split():
     if lib:
         lego_ba._balib = None

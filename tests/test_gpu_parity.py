@@ -18,7 +18,7 @@ import pytest
 import lego_ba
 import oracle_bind as ob
 from align import aligned_errors, oracle_state_spread
-from windows import window
+from windows import stable_window, window
 
 pytestmark = pytest.mark.gpu
 
@@ -331,14 +331,6 @@ def test_largest_lds_window_p21():
     assert rel(g["chi2_final"], o["chi2_final"]) < max(1e-6, 10 * spread)
 
 
-def _stable_window(P, L, seed, **kw):
-    w = lego_ba.generate_window(P=P, L=L, k=8, seed=seed, **dict(__import__("windows").STABLE, outlier_frac=0.0), **kw)
-    f = np.zeros(P, np.uint8)
-    f[0] = 1
-    w["pose_fixed"] = f
-    return w
-
-
 @pytest.mark.parametrize("P,L,seed,mode", [(22, 3000, 4, 0), (32, 4000, 1, 0), (40, 3000, 3, 1), (64, 6000, 2, 0)])
 def test_large_windows_global_memory_solve(P, L, seed, mode):
     """Windows past 21 keyframes (the reference solver takes any number, problem.cpp:277-279).
@@ -348,7 +340,7 @@ def test_large_windows_global_memory_solve(P, L, seed, mode):
     trial at the single-trial bar, then the full solve at the north-star bar (chi2 1e-6, poses and
     landmarks 1e-6) against the oracle on reproducible windows."""
     kw = dict(pose_mode=1, k_min=2, k_max=8) if mode else {}
-    w = _stable_window(P, L, seed, **kw)
+    w = stable_window(P, L, seed, **kw)
     s1 = lego_ba.Solver(max_iters=1, max_trials=1)
     g = s1.solve(w)
     assert s1.controller() == ("k_ctrl_g" if mode else "k_ctrl_b")
@@ -371,7 +363,7 @@ def test_banded_ldlt_past_64_keyframes(P, L, seed):
     controller (k_ctrl_b) streams the band of S through one CU's LDS.  One trial at the single-trial
     bar, the full solve at the north-star bar against the oracle's LDLT (windows the oracle reproduces
     across thread counts)."""
-    w = _stable_window(P, L, seed)
+    w = stable_window(P, L, seed)
     s1 = lego_ba.Solver(max_iters=1, max_trials=1)
     g = s1.solve(w)
     assert s1.controller() == "k_ctrl_b"
@@ -394,7 +386,7 @@ def test_banded_back_substitution_row_windows(monkeypatch):
     its 8-row block (8-keyframe runs: 47 rows), two rows per lane otherwise.  A row takes the same products
     in the same order either way, so on a narrow window the two forms agree bitwise (LH_NO_NARROW=1 forces
     the two-row form)."""
-    w = _stable_window(128, 8000, 3)
+    w = stable_window(128, 8000, 3)
     s = lego_ba.Solver()
     a = s.solve(w)
     assert s.controller() == "k_ctrl_b" and s.band_narrow()

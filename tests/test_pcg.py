@@ -16,7 +16,7 @@ import pytest
 
 import lego_ba
 import oracle_bind as ob
-from windows import window
+from windows import stable_window, window
 
 
 def spd_system(n, seed):
@@ -134,15 +134,6 @@ def test_gpu_pcg_c3_window():
 
 
 # ------------------------------------------------------------------ GPU: many-keyframe windows (k_ctrl_p)
-def _many_pose_window(P, L, seed, **kw):
-    from windows import STABLE
-    w = lego_ba.generate_window(P=P, L=L, k=8, seed=seed, **dict(STABLE, outlier_frac=0.0), **kw)
-    f = np.zeros(P, np.uint8)
-    f[0] = 1
-    w["pose_fixed"] = f
-    return w
-
-
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("P,L,seed,kw", [(22, 2000, 1, {}), (40, 3000, 2, {}), (64, 4000, 2, {}), (96, 5000, 3, {}),
@@ -155,7 +146,7 @@ def test_gpu_pcg_many_keyframes(P, L, seed, kw):
     reproducible: the oracle's PCG and LDLT solves agree on iterations and trials across thread counts
     (128 keyframes seed 1 rejects 12 of its 20 trials).  Windows of random keyframe subsets stall at
     different trials under reordering even in the oracle, so they are not used here."""
-    w = _many_pose_window(P, L, seed, **kw)
+    w = stable_window(P, L, seed, **kw)
     g1 = lego_ba.Solver(linear_solver=lego_ba.LH_SOLVER_PCG, max_iters=1, max_trials=1).solve(w)
     o1 = ob.solve(w, linear_solver=1, max_iters=1, max_trials=1)
     # the residual stop is crossed within a few steps of the oracle's (rounding in S and the dots)
@@ -179,7 +170,7 @@ def test_gpu_pcg_many_keyframes(P, L, seed, kw):
 @pytest.mark.gpu
 def test_many_keyframes_envelope():
     """Past 64 keyframes a banded window runs LDLT (k_ctrl_b) as well as PCG (k_ctrl_p, up to 256)."""
-    w = _many_pose_window(80, 2000, 5)
+    w = stable_window(80, 2000, 5)
     s = lego_ba.Solver(max_iters=2)
     a = s.solve(w)
     assert s.controller() == "k_ctrl_b" and a["chi2_final"] < a["chi2_initial"]

@@ -54,6 +54,13 @@ def window_shard(cfg, l0, l1, seed=0, family="default", fix_first=None, **kw):
     return _fix(lego_ba.generate_window(seed=seed, lm_begin=l0, lm_end=l1, **c), fix_first)
 
 
+def stable_window(P, L, seed, **kw):
+    """A STABLE window of P keyframes without outliers, pose 0 fixed: landmarks seen by runs of 8 consecutive
+    keyframes (a banded reduced system) unless kw says otherwise."""
+    w = lego_ba.generate_window(P=P, L=L, k=8, seed=seed, **dict(STABLE, outlier_frac=0.0), **kw)
+    return _fix(w, True)
+
+
 def _rot(axis, angle):
     a = np.asarray(axis, np.float64)
     a = a / np.linalg.norm(a)
