@@ -54,11 +54,30 @@ __device__ unsigned long long lh_stamps[256];   // [64, 128): k_ctrl's LDL^T ste
             __builtin_amdgcn_sched_barrier(0);                                     \
         }                                                                          \
     } while (0)
+// a controller's launch: its start times taken at the top, added with the live-launch count once the launch is
+// known to be live (after the decision's exits), and the end time
+#define CSTAMP_START \
+    const unsigned long long ct_start = __builtin_amdgcn_s_memtime(), rt_start = __builtin_amdgcn_s_memrealtime()
+#define CSTAMP_LIVE()                                                              \
+    do {                                                                           \
+        if (threadIdx.x == 0) {                                                    \
+            atomicAdd(&lh_stamps[32], ct_start);                                   \
+            atomicAdd(&lh_stamps[61], 1ull);                                       \
+            atomicAdd(&lh_stamps[62], rt_start);                                   \
+        }                                                                          \
+    } while (0)
+#define CSTAMP_END()                                                               \
+    do {                                                                           \
+        if (threadIdx.x == 0) atomicAdd(&lh_stamps[63], (unsigned long long)__builtin_amdgcn_s_memrealtime()); \
+    } while (0)
 #else
 #define STAMP_DECL
 #define STAMP(i)
 #define STAMP_FLUSH(base, cnt)
 #define CSTAMP(i)
+#define CSTAMP_START
+#define CSTAMP_LIVE()
+#define CSTAMP_END()
 #endif
 
 __device__ __forceinline__ double readlane_d(double v, int l) {
@@ -1551,6 +1570,18 @@ __device__ __forceinline__ void batch_load(const lh_ctrl* __restrict__ ctrl, Bat
     cnt[BW_PCG] = ctrl->pcg_iters;
     cnt[BW_LSKIP] = 0;
 }
+// a self-deciding controller's: the words it loaded, the rungs' arrays left in lh_ctrl (global: one load per rung)
+__device__ __forceinline__ BatchWords batch_words(const lh_ctrl* __restrict__ ctrl, const CtrlWords& cw, int* cnt) {
+    BatchWords b;
+    b.w = cw;
+    b.sp = ctrl->spose_l;
+    b.lad_its = ctrl->lad_its;
+    b.cnt = cnt;
+    cnt[BW_LSKIPS] = ctrl->lskips;
+    cnt[BW_PCG] = ctrl->pcg_iters;
+    cnt[BW_LSKIP] = 0;
+    return b;
+}
 
 // a batch's words after its last decision (what ctrl_lm_step stores after a decision, from the batch's registers)
 __device__ __forceinline__ void batch_store(lh_ctrl* __restrict__ ctrl, const BatchWords& b, int seq) {
@@ -1884,27 +1915,16 @@ __device__ __forceinline__ int ctrl_batch_decide(lh_ctrl* __restrict__ ctrl, Bat
     return batch_finish(ctrl, bw, prm, r, host_done, seq, raise_done, done_o, accept_o, cur_o, lam_o);
 }
 // a self-deciding controller's decision (thread 0): a batch's (this chain's evo word above its low byte, the
-// rungs' scalars behind the exchanged system, lh_rs_layout.off_bsc) or one trial's.  BATCH false: the caller's
-// batches are decided elsewhere (k_ctrl: its decider workgroup, ctrl_batch_decider)
-template <bool BATCH = true>
+// rungs' scalars behind the exchanged system, lh_rs_layout.off_bsc) or one trial's
 __device__ __forceinline__ int ctrl_decide(lh_ctrl* __restrict__ ctrl, const CtrlWords& cw, const lh_params& prm, int mode,
                                            double mdiag, double tchi, double sl, double ndg, const double* rs_stage,
                                            const lh_rs_layout& LY, volatile int* __restrict__ host_done, int seq,
                                            int& done_o, int& accept_o, int& cur_o, double& lam_o, int* cnt) {
-    if constexpr (BATCH) {
-        const int nb = cw.evo >> 8;   // (cw.evo: this chain's evo word, read before its decision)
-        if (mode != 0 && nb > 1) {
-            BatchWords bw;
-            bw.w = cw;
-            bw.sp = ctrl->spose_l;   // (global: one load per rung)
-            bw.lad_its = ctrl->lad_its;
-            bw.cnt = cnt;
-            cnt[BW_LSKIPS] = ctrl->lskips;
-            cnt[BW_PCG] = ctrl->pcg_iters;
-            cnt[BW_LSKIP] = 0;
-            return ctrl_batch_decide(ctrl, bw, prm, rs_stage + LY.off_bsc, nb, host_done, seq, true, done_o, accept_o,
-                                     cur_o, lam_o);
-        }
+    const int nb = cw.evo >> 8;   // (cw.evo: this chain's evo word, read before its decision)
+    if (mode != 0 && nb > 1) {
+        BatchWords bw = batch_words(ctrl, cw, cnt);
+        return ctrl_batch_decide(ctrl, bw, prm, rs_stage + LY.off_bsc, nb, host_done, seq, true, done_o, accept_o, cur_o,
+                                 lam_o);
     }
     return ctrl_lm_step(ctrl, cw, prm, mode, mdiag, tchi, sl, ndg, host_done, seq, done_o, accept_o, cur_o, lam_o);
 }
@@ -1954,14 +1974,7 @@ __device__ __forceinline__ void ctrl_decider(lh_ctrl* __restrict__ ctrl, const l
     int d_o, a_o, c_o;
     double l_o;
     if (nb > 1) {
-        BatchWords bw;
-        bw.w = ctrl_load(ctrl);
-        bw.sp = ctrl->spose_l;
-        bw.lad_its = ctrl->lad_its;
-        bw.cnt = cnt;
-        cnt[BW_LSKIPS] = ctrl->lskips;
-        cnt[BW_PCG] = ctrl->pcg_iters;
-        cnt[BW_LSKIP] = 0;
+        BatchWords bw = batch_words(ctrl, ctrl_load(ctrl), cnt);
         ctrl_batch_decide(ctrl, bw, prm, rs_stage + LY.off_bsc, nb, host_done, seq, true, d_o, a_o, c_o, l_o);
     } else {
         const CtrlWords cw = ctrl_load(ctrl);
@@ -1974,6 +1987,96 @@ __device__ __forceinline__ void ctrl_decider(lh_ctrl* __restrict__ ctrl, const l
 // a factoring controller's rung count: prm.ladder rungs at every factor (ladder_eager) or a factor after a rejection
 __device__ __forceinline__ bool ladder_build(const lh_params& prm, int accept) {
     return prm.ladder > 1 && (prm.ladder_eager || !accept);
+}
+
+// ---- a controller launch's LM decision: k_ctrl_g, k_ctrl_b, k_ctrl_p (DESIGN.md 2.2a "Who decides") ----
+// Every workgroup of the launch calls this first, all NT threads.  The decision is k_reduce's
+// (prm.dec_in_reduce: read from lh_ctrl, in registers), workgroup 0's (a rung waits for its tag, then reads it
+// the same way), or taken here by workgroup 0's thread 0 and broadcast through the kernel's CtrlDecLds.  Then
+// the exits every controller shares, and the ladder's rung count.  run false: the kernel returns.  s_red: NT / 64
+// doubles of the kernel's (its step tail reuses them).
+struct CtrlDecLds {
+    int flags[4];   // done, accept, cur, nothing to factor
+    int cnt[4];     // a batch's counters (BatchWords::cnt)
+    double lam;
+};
+struct CtrlDec {
+    bool run;
+    int accept, cur;
+    double lambda;
+};
+template <int NT>
+__device__ __forceinline__ CtrlDec ctrl_take_decision(lh_ctrl* __restrict__ ctrl, const lh_params& prm, int mode,
+                                                      const double* __restrict__ rs_stage, const lh_rs_layout& LY,
+                                                      const double* __restrict__ maxd_in,
+                                                      volatile int* __restrict__ host_done, int seq, double* s_red,
+                                                      CtrlDecLds& lds) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = 6 * prm.P;
+    const int rung = (int)blockIdx.x;   // workgroup `rung` > 0: a lambda-ladder rung with its own factor storage
+    const bool dec_src = mode != 0 && prm.dec_in_reduce;
+    CtrlDec o{false, 0, 0, 0.0};
+#ifdef LH_STAMPS
+    if (rung) return o;   // (the diagnostic build times one controller)
+#endif
+    if (rung && mode == 0) return o;   // (the initial linearisation builds no ladder, as k_ctrl)
+    if (rung && !dec_src) ladder_wait(ctrl, seq);   // workgroup 0 decides and publishes
+    int done, skip;
+    if (dec_src || rung) {
+        const LadderDec d = ladder_read(ctrl, prm, seq, rung);
+        done = d.done;
+        o.accept = d.accept;
+        skip = d.skip;
+        o.lambda = d.lambda;
+        o.cur = __builtin_amdgcn_readfirstlane(ctrl->cur);
+        // this trial's k_reduce stopped the loop: the host's done is raised here (ctrl_lm_step)
+        if (dec_src && done && tid == 0 && host_done && ctrl->done_seq == seq && rung == 0) publish_stop(ctrl, host_done);
+    } else {
+        double tchi = 0.0, sl = 0.0, ndg = 0.0;
+        CtrlWords cw{};
+        if (tid == 0) {
+            cw = ctrl_load(ctrl);
+            tchi = 0.5 * rs_stage[LY.off_sc + LH_SC_CHI2];
+            sl = rs_stage[LY.off_sc + LH_SC_SCALE];
+            ndg = rs_stage[LY.off_sc + LH_SC_NDEG];
+        }
+        if (mode == 0) {   // max |diag H_pp| for computeLambdaInitLM (problem.cpp:486-496)
+            double mx = 0.0;
+            for (int i = tid; i < n; i += NT) mx = fmax(mx, fabs(rs_stage[LY.off_hd + i]));
+            for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+            if (lane == 0) s_red[wave] = mx;
+            lds_barrier();
+        }
+        if (tid == 0) {
+            double mdiag = 0.0;
+            if (mode == 0) {
+                for (int w = 0; w < NT / 64; ++w) mdiag = fmax(mdiag, s_red[w]);
+                mdiag = fmax(*maxd_in, mdiag);
+            }
+            int d_o, a_o, c_o;
+            double lam_n;
+            lds.flags[3] = ctrl_decide(ctrl, cw, prm, mode, mdiag, tchi, sl, ndg, rs_stage, LY, host_done, seq, d_o, a_o,
+                                       c_o, lam_n, lds.cnt);
+            if (prm.ladder > 1 && mode != 0) ladder_publish(ctrl, seq);   // the rung workgroups wait for it
+            lds.flags[0] = d_o;
+            lds.flags[1] = a_o;
+            lds.flags[2] = c_o;
+            lds.lam = lam_n;
+        }
+        lds_barrier();
+        done = lds.flags[0];
+        o.accept = lds.flags[1];
+        o.cur = lds.flags[2];
+        skip = lds.flags[3];
+        o.lambda = lds.lam;
+    }
+    if (done || skip) return o;   // stopped, an evaluate-only acceptance, or a rejection onto a built rung
+    // the ladder: a factor builds prm.ladder rungs (every factor, or with ladder_eager off only one after a
+    // rejection); rung r factors at the lambda r more rejections set (ladder_read)
+    const bool build = mode != 0 && ladder_build(prm, o.accept);
+    if (rung != 0 && (!build || rung >= prm.ladder)) return o;
+    if (rung == 0 && tid == 0) ctrl->lad_n = build ? prm.ladder : 1;
+    o.run = true;
+    return o;
 }
 
 // ============================================================================
@@ -3101,6 +3204,9 @@ __global__ __launch_bounds__(CT) void k_ctrl(lh_ctrl* __restrict__ ctrl, double*
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int P = prm.P, n = 6 * P, NE = (n + 15) & ~15;
     const lh_rs_layout LY = lh_rs_make(P, prm.npairs);
+    // The other controllers take the launch's decision in one call (ctrl_take_decision).  This one spells the same
+    // protocol out, spread through its prefetch: the system's loads and wave 0's early block-0 factor overlap the
+    // decision's reads, and at 1024 threads on 128 VGPRs small changes to this prologue have spilled twice.
     // k_reduce took this trial's LM decision; a rung workgroup > 0 reads it (or workgroup 0's) from lh_ctrl
     const int rung = (int)blockIdx.x;
     const bool dec_src = mode != 0 && prm.dec_in_reduce;
@@ -3125,8 +3231,8 @@ __global__ __launch_bounds__(CT) void k_ctrl(lh_ctrl* __restrict__ ctrl, double*
     constexpr int CW = CT - 64, IMG2 = LH_IMG_SZ / 2, NIMG = (IMG2 + CW - 1) / CW;
     const int ctid = tid - 64;
     const bool cpw = tid >= 64;
+    CSTAMP_START;
 #ifdef LH_STAMPS
-    const unsigned long long ct_start = __builtin_amdgcn_s_memtime(), rt_start = __builtin_amdgcn_s_memrealtime();
     // [160 + wave]: the wave's HW_ID word (SIMD in bits 5:4): which waves share wave 0's SIMD
     if (lane == 0) lh_stamps[160 + wave] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4) | (1ull << 32);
 #endif
@@ -3266,29 +3372,26 @@ __global__ __launch_bounds__(CT) void k_ctrl(lh_ctrl* __restrict__ ctrl, double*
 #endif
     }
 
-    if (!decided) {
-        if (mode == 0) {   // max |diag H_pp| for computeLambdaInitLM (problem.cpp:486-496)
-            double mx = 0.0;
-            if constexpr (imgp) {
-                if (tid < n) mx = fabs(hdx);
-            } else {
+    if (!decided) {   // (only the initial linearisation, mode 0, on workgroup 0)
+        // max |diag H_pp| for computeLambdaInitLM (problem.cpp:486-496)
+        double mx = 0.0;
+        if constexpr (imgp) {
+            if (tid < n) mx = fabs(hdx);
+        } else {
 #pragma unroll
-                for (int u = 0; u < NLD; ++u) {
-                    const int i = u * ER + ibase;
-                    if (i >= LY.off_hd && i < LY.off_hd + n) mx = fmax(mx, fabs(vs[u]));
-                }
+            for (int u = 0; u < NLD; ++u) {
+                const int i = u * ER + ibase;
+                if (i >= LY.off_hd && i < LY.off_hd + n) mx = fmax(mx, fabs(vs[u]));
             }
-            for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-            if (lane == 0) s_red[wave] = mx;
-            lds_barrier();
         }
+        for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+        if (lane == 0) s_red[wave] = mx;
+        lds_barrier();
         // ---------------- LM bookkeeping (thread 0) ----------------
         if (tid == 0) {
             double mdiag = 0.0;
-            if (mode == 0) {
-                for (int w = 0; w < CT / 64; ++w) mdiag = fmax(mdiag, s_red[w]);
-                mdiag = fmax(*maxd_in, mdiag);
-            }
+            for (int w = 0; w < CT / 64; ++w) mdiag = fmax(mdiag, s_red[w]);
+            mdiag = fmax(*maxd_in, mdiag);
             int d_o, a_o, c_o;
             double lam_n;
             // (only the initial linearisation's: a later chain's is the decider workgroup's)
@@ -3312,13 +3415,7 @@ __global__ __launch_bounds__(CT) void k_ctrl(lh_ctrl* __restrict__ ctrl, double*
     if (rung != 0 && (!build || rung >= prm.ladder)) return;
     if (rung == 0 && tid == 0) ctrl->lad_n = build ? prm.ladder : 1;
     dxp += (size_t)rung * n;
-#ifdef LH_STAMPS
-    if (tid == 0) {
-        atomicAdd(&lh_stamps[32], ct_start);
-        atomicAdd(&lh_stamps[61], 1ull);
-        atomicAdd(&lh_stamps[62], rt_start);
-    }
-#endif
+    CSTAMP_LIVE();
     CSTAMP(1);
 #ifdef LH_STAMPS
     if (tid == 0) __builtin_amdgcn_s_waitcnt(0);   // (diagnostic) thread 0's staged-system loads have arrived
@@ -3446,9 +3543,7 @@ __global__ __launch_bounds__(CT) void k_ctrl(lh_ctrl* __restrict__ ctrl, double*
     // the one-chain LDL^T took the tail in its back-substitution wave
     if (SOLVER == 1 || nd) ctrl_step_tail<CT>(ctrl, prm, n, lambda, xs, bpv, hdv, s_red, dxp, rung);
     CSTAMP(12);
-#ifdef LH_STAMPS
-    if (tid == 0) atomicAdd(&lh_stamps[63], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-#endif
+    CSTAMP_END();
 }
 
 // ============================================================================
@@ -3720,87 +3815,24 @@ __global__ __launch_bounds__(GT) void k_ctrl_g(lh_ctrl* __restrict__ ctrl, doubl
     __shared__ double pnl[GNMAX * GPS];
     __shared__ double dg[GNMAX], bsv[GNMAX], bpv[GNMAX], hdv[GNMAX], xs[GNMAX], yv[GNMAX], gkey[GNMAX];
     __shared__ int perm[GNMAX], iperm[GNMAX];
-    __shared__ int s_flags[4];
-    __shared__ double s_red[GT / 64], s_lam;
+    __shared__ double s_red[GT / 64];
+    __shared__ CtrlDecLds s_dec;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int P = prm.P, n = 6 * P, NG = (n + GNB - 1) & ~(GNB - 1);
     const lh_rs_layout LY = lh_rs_make(P, prm.npairs);
-#ifdef LH_STAMPS
-    const unsigned long long ct_start = __builtin_amdgcn_s_memtime(), rt_start = __builtin_amdgcn_s_memrealtime();
-#endif
+    CSTAMP_START;
 
-    // ---------------- controller words, pose matrices, max |diag| (mode 0) ----------------
-    // workgroup `rung` > 0: a lambda-ladder rung with its own gA; it waits for workgroup 0's decision
+    // ---------------- the LM decision (workgroup `rung` > 0: a lambda-ladder rung with its own gA) ----------------
     const int rung = (int)blockIdx.x;
-#ifdef LH_STAMPS
-    if (rung) return;
-#endif
-    if (rung && mode == 0) return;   // (the initial linearisation builds no ladder, as k_ctrl)
-    if (rung) {
-        ladder_wait(ctrl, seq);
-        const LadderDec d = ladder_read(ctrl, prm, seq, rung);
-        if (tid == 0) {
-            s_flags[0] = d.done;
-            s_flags[1] = d.accept;
-            s_flags[2] = ctrl->cur;
-            s_flags[3] = d.skip;
-            s_lam = d.lambda;
-        }
-        lds_barrier();
-    }
-    double tchi = 0.0, sl = 0.0, ndg = 0.0;
-    CtrlWords cw{};
-    if (tid == 0 && !rung) {
-        cw = ctrl_load(ctrl);
-        tchi = 0.5 * rs_stage[LY.off_sc + LH_SC_CHI2];
-        sl = rs_stage[LY.off_sc + LH_SC_SCALE];
-        ndg = rs_stage[LY.off_sc + LH_SC_NDEG];
-    }
-    if (!rung) {
-        double mx = 0.0;
-        if (mode == 0)
-            for (int i = tid; i < n; i += GT) mx = fmax(mx, fabs(rs_stage[LY.off_hd + i]));
-        for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-        if (lane == 0) s_red[wave] = mx;
-    }
-    lds_barrier();
-    if (tid == 0 && !rung) {
-        double mdiag = 0.0;
-        if (mode == 0) {
-            for (int w = 0; w < GT / 64; ++w) mdiag = fmax(mdiag, s_red[w]);
-            mdiag = fmax(*maxd_in, mdiag);
-        }
-        int done, accept, cur;
-        double lam_n;
-        __shared__ int b_cnt[4];
-        s_flags[3] = ctrl_decide(ctrl, cw, prm, mode, mdiag, tchi, sl, ndg, rs_stage, LY, host_done, seq, done, accept, cur,
-                                 lam_n, b_cnt);
-        if (prm.ladder > 1 && mode != 0) ladder_publish(ctrl, seq);   // the rung workgroups wait for it
-        s_flags[0] = done;
-        s_flags[1] = accept;
-        s_flags[2] = cur;
-        s_lam = lam_n;
-    }
-    lds_barrier();
-    const int done = s_flags[0], accept = s_flags[1], cur = s_flags[2];
-    if (done || s_flags[3]) return;   // stopped, an evaluate-only acceptance, or a rejection onto a built rung
-    const double lambda = s_lam;
-    {
-        const bool build = mode != 0 && ladder_build(prm, accept);
-        if (rung != 0 && (!build || rung >= prm.ladder)) return;
-        if (rung == 0 && tid == 0) ctrl->lad_n = build ? prm.ladder : 1;
-        gA += (size_t)rung * prm.lad_stride;
-        dxp += (size_t)rung * n;
-    }
+    const CtrlDec dec = ctrl_take_decision<GT>(ctrl, prm, mode, rs_stage, LY, maxd_in, host_done, seq, s_red, s_dec);
+    if (!dec.run) return;
+    const int accept = dec.accept, cur = dec.cur;
+    const double lambda = dec.lambda;
+    gA += (size_t)rung * prm.lad_stride;
+    dxp += (size_t)rung * n;
 
-#ifdef LH_STAMPS
-    if (tid == 0) {
-        atomicAdd(&lh_stamps[32], ct_start);
-        atomicAdd(&lh_stamps[61], 1ull);
-        atomicAdd(&lh_stamps[62], rt_start);
-    }
-#endif
+    CSTAMP_LIVE();
     CSTAMP(1);
 
     // ---------------- diagonal + lambda and right-hand sides (one round trip) ----------------
@@ -3885,9 +3917,7 @@ __global__ __launch_bounds__(GT) void k_ctrl_g(lh_ctrl* __restrict__ ctrl, doubl
     CSTAMP(8);
     ctrl_step_tail<GT>(ctrl, prm, n, lambda, xs, bpv, hdv, s_red, nullptr, rung);
     CSTAMP(12);
-#ifdef LH_STAMPS
-    if (tid == 0) atomicAdd(&lh_stamps[63], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-#endif
+    CSTAMP_END();
 }
 
 // ============================================================================
@@ -3948,90 +3978,24 @@ __global__ __launch_bounds__(CT) void k_ctrl_b(lh_ctrl* __restrict__ ctrl, const
     __shared__ __attribute__((aligned(16))) double y[BNMAX];   // rhs (forward substitution), then x
     __shared__ double z[BNMAX];                             // D^-1 L^-1 b
     __shared__ __attribute__((aligned(16))) double Nl[2][64], NDl[2][64];
-    __shared__ int s_flags[4];
-    __shared__ double s_red[CT / 64], s_lam;
+    __shared__ double s_red[CT / 64];
+    __shared__ CtrlDecLds s_dec;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     const int P = prm.P, n = 6 * P, NE = (n + 15) & ~15, nb = (n + 7) & ~7, NT = NE / 16, nstep = nb / 8;
     const lh_rs_layout LY = lh_rs_make(P, prm.npairs);
-    // workgroup `rung` > 0: a lambda-ladder rung (k_ctrl's scheme), with its own L rows and ND
     const int rung = (int)blockIdx.x;
-    const bool dec_src = mode != 0 && prm.dec_in_reduce;
-    const bool decided = dec_src || rung > 0;
-#ifdef LH_STAMPS
-    const unsigned long long ct_start = __builtin_amdgcn_s_memtime(), rt_start = __builtin_amdgcn_s_memrealtime();
-#endif
-    // ---------------- the decision ----------------
-    int done = 0, accept = 0, skip = 0;
-    double lambda = 0.0;
-#ifdef LH_STAMPS
-    if (rung) return;
-#endif
-    if (rung && mode == 0) return;   // (the initial linearisation builds no ladder, as k_ctrl)
-    if (rung && !dec_src) ladder_wait(ctrl, seq);   // workgroup 0 decides and publishes
-    if (decided) {
-        const LadderDec d = ladder_read(ctrl, prm, seq, rung);
-        done = d.done;
-        accept = d.accept;
-        skip = d.skip;
-        lambda = d.lambda;
-        // this trial's k_reduce stopped the loop: the host's done is raised here (ctrl_lm_step)
-        if (dec_src && done && tid == 0 && host_done && ctrl->done_seq == seq && rung == 0) publish_stop(ctrl, host_done);
-    } else {
-        double tchi = 0.0, sl = 0.0, ndg = 0.0;
-        CtrlWords cw{};
-        if (tid == 0) {
-            cw = ctrl_load(ctrl);
-            tchi = 0.5 * rs_stage[LY.off_sc + LH_SC_CHI2];
-            sl = rs_stage[LY.off_sc + LH_SC_SCALE];
-            ndg = rs_stage[LY.off_sc + LH_SC_NDEG];
-        }
-        double mx = 0.0;
-        if (mode == 0)
-            for (int i = tid; i < n; i += CT) mx = fmax(mx, fabs(rs_stage[LY.off_hd + i]));
-        for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-        if (lane == 0) s_red[wave] = mx;
-        lds_barrier();
-        if (tid == 0) {
-            double mdiag = 0.0;
-            if (mode == 0) {
-                for (int w = 0; w < CT / 64; ++w) mdiag = fmax(mdiag, s_red[w]);
-                mdiag = fmax(*maxd_in, mdiag);
-            }
-            int d_o, a_o, c_o;
-            double lam_n;
-            __shared__ int b_cnt[4];
-            s_flags[2] = ctrl_decide(ctrl, cw, prm, mode, mdiag, tchi, sl, ndg, rs_stage, LY, host_done, seq, d_o, a_o, c_o,
-                                     lam_n, b_cnt);
-            if (prm.ladder > 1 && mode != 0) ladder_publish(ctrl, seq);   // the rung workgroups wait for it
-            s_flags[0] = d_o;
-            s_flags[1] = a_o;
-            s_lam = lam_n;
-        }
-        lds_barrier();
-        done = s_flags[0];
-        accept = s_flags[1];
-        skip = s_flags[2];
-        lambda = s_lam;
-    }
-    if (done || skip) return;
-    {
-        const bool build = mode != 0 && ladder_build(prm, accept);
-        if (rung != 0 && (!build || rung >= prm.ladder)) return;
-        if (rung == 0 && tid == 0) ctrl->lad_n = build ? prm.ladder : 1;
-        const size_t NEs = (size_t)NE;
-        Lg += (size_t)rung * (NEs * LH_LBW + (size_t)BSTEP_MAX * 64);   // lh_band_args: per rung, L rows | ND
-        NDg += (size_t)rung * (NEs * LH_LBW + (size_t)BSTEP_MAX * 64);
-        dxp += (size_t)rung * n;
-    }
-#ifdef LH_STAMPS
-    if (tid == 0) {
-        atomicAdd(&lh_stamps[32], ct_start);
-        atomicAdd(&lh_stamps[61], 1ull);
-        atomicAdd(&lh_stamps[62], rt_start);
-    }
-#endif
+    CSTAMP_START;
+    // ---------------- the LM decision (workgroup `rung` > 0: a lambda-ladder rung with its own L rows and ND) ----------------
+    const CtrlDec dec = ctrl_take_decision<CT>(ctrl, prm, mode, rs_stage, LY, maxd_in, host_done, seq, s_red, s_dec);
+    if (!dec.run) return;
+    const int accept = dec.accept;
+    const double lambda = dec.lambda;
+    Lg += (size_t)rung * ((size_t)NE * LH_LBW + (size_t)BSTEP_MAX * 64);   // lh_band_args: per rung, L rows | ND
+    NDg += (size_t)rung * ((size_t)NE * LH_LBW + (size_t)BSTEP_MAX * 64);
+    dxp += (size_t)rung * n;
+    CSTAMP_LIVE();
     CSTAMP(1);
     const double* __restrict__ src = accept ? rs_stage : rs_commit;
     // prm.bimg: k_reduce wrote the band in the loaders' order (lh_bimg_idx; staged, then committed): one load per
@@ -4437,9 +4401,7 @@ __global__ __launch_bounds__(CT) void k_ctrl_b(lh_ctrl* __restrict__ ctrl, const
     CSTAMP(8);
     ctrl_step_tail<CT>(ctrl, prm, n, lambda, y, src + LY.off_bp, src + LY.off_hd, s_red, dxp, rung);
     CSTAMP(12);
-#ifdef LH_STAMPS
-    if (tid == 0) atomicAdd(&lh_stamps[63], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-#endif
+    CSTAMP_END();
 }
 
 // ============================================================================
@@ -4479,77 +4441,21 @@ __global__ __launch_bounds__(CT) void k_ctrl_p(lh_ctrl* __restrict__ ctrl, doubl
                                                int mode, volatile int* __restrict__ host_done, int seq,
                                                double* __restrict__ ell) {
     __shared__ double pv[PNMAX], bpv[PNMAX], hdv[PNMAX], xs[PNMAX];
-    __shared__ int s_flags[4];
     __shared__ __attribute__((aligned(16))) double s_red[3][CT / 64];
-    __shared__ double s_lam;
+    __shared__ CtrlDecLds s_dec;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int P = prm.P, n = 6 * P;
     const lh_rs_layout LY = lh_rs_make(P, prm.npairs);
 
-    // ---------------- controller words, pose matrices, max |diag| (mode 0), the LM decision ----------------
-    // workgroup `rung` > 0: a lambda-ladder rung with its own row copy of S; it waits for workgroup
-    // 0's decision
+    // ---------------- the LM decision (workgroup `rung` > 0: a lambda-ladder rung with its own row copy of S) ----------------
     const int rung = (int)blockIdx.x;
-#ifdef LH_STAMPS
-    if (rung) return;
-#endif
-    if (rung && mode == 0) return;   // (the initial linearisation builds no ladder, as k_ctrl)
-    if (rung) {
-        ladder_wait(ctrl, seq);
-        const LadderDec d = ladder_read(ctrl, prm, seq, rung);
-        if (tid == 0) {
-            s_flags[0] = d.done;
-            s_flags[1] = d.accept;
-            s_flags[3] = d.skip;
-            s_lam = d.lambda;
-        }
-        lds_barrier();
-    }
-    double tchi = 0.0, sl = 0.0, ndg = 0.0;
-    CtrlWords cw{};
-    if (tid == 0 && !rung) {
-        cw = ctrl_load(ctrl);
-        tchi = 0.5 * rs_stage[LY.off_sc + LH_SC_CHI2];
-        sl = rs_stage[LY.off_sc + LH_SC_SCALE];
-        ndg = rs_stage[LY.off_sc + LH_SC_NDEG];
-    }
-    if (!rung) {
-        double mx = 0.0;
-        if (mode == 0)
-            for (int i = tid; i < n; i += CT) mx = fmax(mx, fabs(rs_stage[LY.off_hd + i]));
-        for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-        if (lane == 0) s_red[0][wave] = mx;
-    }
-    lds_barrier();
-    if (tid == 0 && !rung) {
-        double mdiag = 0.0;
-        if (mode == 0) {
-            for (int w = 0; w < CT / 64; ++w) mdiag = fmax(mdiag, s_red[0][w]);
-            mdiag = fmax(*maxd_in, mdiag);
-        }
-        int done, accept, cur;
-        double lam_n;
-        __shared__ int b_cnt[4];
-        s_flags[3] = ctrl_decide(ctrl, cw, prm, mode, mdiag, tchi, sl, ndg, rs_stage, LY, host_done, seq, done, accept, cur,
-                                 lam_n, b_cnt);
-        if (prm.ladder > 1 && mode != 0) ladder_publish(ctrl, seq);   // the rung workgroups wait for it
-        s_flags[0] = done;
-        s_flags[1] = accept;
-        s_flags[2] = cur;
-        s_lam = lam_n;
-    }
-    lds_barrier();
-    const int done = s_flags[0], accept = s_flags[1];
-    if (done || s_flags[3]) return;   // stopped, an evaluate-only acceptance, or a rejection onto a built rung
-    const double lambda = s_lam;
-    {
-        const bool build = mode != 0 && ladder_build(prm, accept);
-        if (rung != 0 && (!build || rung >= prm.ladder)) return;
-        if (rung == 0 && tid == 0) ctrl->lad_n = build ? prm.ladder : 1;
-        ell += (size_t)rung * prm.lad_stride;
-        dxp += (size_t)rung * n;
-    }
+    const CtrlDec dec = ctrl_take_decision<CT>(ctrl, prm, mode, rs_stage, LY, maxd_in, host_done, seq, s_red[0], s_dec);
+    if (!dec.run) return;
+    const int accept = dec.accept;
+    const double lambda = dec.lambda;
+    ell += (size_t)rung * prm.lad_stride;
+    dxp += (size_t)rung * n;
 
     // ---------------- the chosen system (the candidate's on accept, committed on it; else the committed one) ----------------
     const double* __restrict__ src = accept ? rs_stage : rs_commit;
