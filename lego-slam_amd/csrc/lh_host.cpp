@@ -5,7 +5,7 @@
 // Per solve nothing but kernel launches happens on the host: the whole LM loop (accept/reject,
 // lambda schedule, stop rule) runs on the device, and the host keeps `depth` trials enqueued ahead
 // of the device's progress word.  With >1 rank each trial carries one all-reduce of the packed
-// reduced pose system; every rank issues exactly the same number of them (see solve_resident_impl).
+// reduced pose system; every rank issues exactly the same number of them (lh_plan.h, the trial schedule).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <sched.h>
@@ -129,6 +129,17 @@ struct HostBuf {
     }
 };
 
+// How the ranks exchange ("One seam"): not at all (one rank), RCCL (also LH_FORCE_RCCL=1 on one rank),
+// LH_COMM_HOST, LH_COMM_P2P.  Decided once in lh_create; only the collective functions switch on it.
+enum Transport { TR_NONE, TR_RCCL, TR_HOST, TR_P2P };
+struct P2pState {
+    DevBuf<double> d_xchg;        // this rank's exchange buffer (lh_common.h), IPC-exported
+    lh_peers peers{};             // every rank's exchange buffer as mapped here (opened IPC handles)
+    long xchg_slot = 0;           // doubles per slot
+    uint32_t solve_gen = 0;       // tags: solves so far (the same count on every rank)
+    int *h_xerr = nullptr, *d_xerr = nullptr;   // host-mapped failure word (a peer's tag did not arrive)
+};
+
 // ---- Eigen quaternion <-> matrix (host copies of the formulas the kernels use) ----
 void q_from_R(const double* R, double q[4]) {
 #define M(i, j) R[3 * (i) + (j)]
@@ -246,15 +257,9 @@ struct lh_handle {
     int device = 0;
     int lds_limit = 160 * 1024;   // hipDeviceAttributeMaxSharedMemoryPerBlock of the device
     hipStream_t stream = nullptr;
-    ncclComm_t comm = nullptr;
-    bool host_comm = false;       // LH_COMM_HOST with world_size > 1
-    bool p2p = false;             // LH_COMM_P2P with world_size > 1 (the caller's all-reduce carries the rest)
-    DevBuf<double> d_xchg;        // P2P: this rank's exchange buffer (lh_common.h), IPC-exported
-    lh_peers peers{};             // every rank's exchange buffer as mapped here (opened IPC handles)
-    long xchg_slot = 0;           // doubles per slot
-    uint32_t solve_gen = 0;       // P2P tags: solves so far (the same count on every rank)
-    int* h_xerr = nullptr;        // P2P: host-mapped failure word (a peer's tag did not arrive)
-    int* d_xerr = nullptr;
+    Transport transport = TR_NONE;
+    ncclComm_t comm = nullptr;    // TR_RCCL's communicator
+    P2pState p2p;                 // TR_P2P's buffers and counters
     bool uploaded = false;
     bool upload_joined = false;   // this upload has taken part in the sharded envelope all-reduce
     bool upload_tail = false;     // ... and every rank passed it: the upload's closing status all-reduce follows
@@ -369,6 +374,12 @@ bool g_debug = getenv("LH_DEBUG") != nullptr;
             return LH_E_RCCL;                                                                            \
         }                                                                                                \
     } while (0)
+
+// What other sites ask of the transport: is the solve sharded; does it exchange one trial at a time on the host
+// (every rank reading the device's stop flag at the same point); has it failed (P2P: a peer's tag did not arrive)
+bool sharded(const lh_handle* h) { return h->transport != TR_NONE; }
+bool exchange_synchronous(const lh_handle* h) { return h->transport == TR_HOST; }
+bool transport_failed(const lh_handle* h) { return h->transport == TR_P2P && *h->p2p.h_xerr; }
 
 hipEvent_t next_event(lh_handle* h) {
     if (h->event_next == h->event_pool.size()) {
@@ -490,23 +501,19 @@ int upload_impl(lh_handle* h, const lh_window* w, bool sync) {
     h->upload_joined = false;
     h->upload_tail = false;
     int st = upload_body(h, w, sync);
-    const bool sharded = h->host_comm || h->comm || h->p2p;
-    if (st != LH_OK && sharded && !h->upload_joined && w && w->n_poses > 0 && w->n_poses <= LH_PMAX_ANY) {
+    if (st != LH_OK && sharded(h) && !h->upload_joined && w && w->n_poses > 0 && w->n_poses <= LH_PMAX_ANY) {
         std::vector<double> buf(1 + (size_t)w->n_poses, -1e300);
         buf[0] = (double)st;
         rank_max(h, buf.data(), 1 + w->n_poses);
     }
-    if (sharded && h->upload_tail) {
+    if (sharded(h) && h->upload_tail) {
         double fs = (double)st;
         const int st_r = rank_max(h, &fs, 1);
         if (st == LH_OK) st = (st_r != LH_OK) ? st_r : (int)fs;
         if (st != LH_OK) h->uploaded = false;
     }
-    // the peer-write exchange's buffers once every rank's upload is through (its collectives run on all ranks)
-    if (st == LH_OK && h->p2p) {
-        st = p2p_setup(h);
-        if (st != LH_OK) h->uploaded = false;
-    }
+    // the peer-write exchange's buffers (P2P only) once every rank's upload is through (its collectives run on all ranks)
+    if (st == LH_OK && (st = p2p_setup(h)) != LH_OK) h->uploaded = false;
     if (st != LH_OK && !h->staging_pending && h->ev_staging) {
         if (hipEventRecord(h->ev_staging, h->stream) == hipSuccess) h->staging_pending = true;
     }
@@ -648,7 +655,7 @@ int window_buffers(lh_handle* h, int ladder) {
     HIPCHK(h->d_ctrl.ensure(1));
     HIPCHK(h->d_out_xyz.ensure(3 * (size_t)pl.L));
     HIPCHK(h->d_out_rho.ensure(pl.O));
-    if (h->host_comm) HIPCHK(h->s_rs.ensure(h->LY.total + 1));
+    if (exchange_synchronous(h)) HIPCHK(h->s_rs.ensure(h->LY.total + 1));   // its pinned copy of the reduced system
     return LH_OK;
 }
 
@@ -724,7 +731,7 @@ ExtFlags pose_tables(lh_handle* h, const lh_window* w) {
 // (allocations, the image initialisation, the copies) is shared by upload_impl's closing status
 // all-reduce.
 int envelope_collective(lh_handle* h, std::vector<int>& pf) {
-    if (!(h->host_comm || h->comm || h->p2p)) return LH_OK;
+    if (!sharded(h)) return LH_OK;
     const int P = h->P;
     std::vector<double> neg(1 + (size_t)P);
     neg[0] = 0.0;
@@ -749,7 +756,7 @@ int configure(lh_handle* h, const std::vector<int>& pf, const lh::Switches& sw) 
     in.linear_solver = h->opt.linear_solver;
     in.max_trials = h->opt.max_trials;
     in.world_size = h->opt.world_size;
-    in.rccl = h->comm != nullptr;
+    in.rccl = h->transport == TR_RCCL;
     in.sw = sw;
     return lh::solve_config(in, h->cfg);
 }
@@ -937,12 +944,34 @@ lh_band_args band_args(lh_handle* h) {
     return lh_band_args{h->d_bblk.p, h->d_bunits.p, h->d_band.p, h->d_band.p + lh::band_scratch(h->P).nd_off};
 }
 
-// P2P: the exchange of chain `seq` (lh_launch_p2p; tags carry the solve count, so no stale tag ever matches)
-hipError_t p2p_exchange(lh_handle* h, int mode, int seq) {
-    const unsigned long long tag = ((unsigned long long)h->solve_gen << 32) | (unsigned long long)(seq + 1);
+// RCCL, P2P: one exchange (mode 0: and max|diag H_ll|) on the stream; next_chain: a top-up, P2P's chain numbers go on
+int exchange_on_stream(lh_handle* h, int mode, bool next_chain) {
+    if (h->transport == TR_P2P) {   // lh_launch_p2p; tags carry the solve count, so no stale tag ever matches
+        const P2pState& x = h->p2p;
+        const int seq = next_chain ? ++h->cur_trial : h->cur_trial;
+        const unsigned long long tag = ((unsigned long long)x.solve_gen << 32) | (unsigned long long)(seq + 1);
+        ++h->n_coll;
+        HIPCHK(lh_launch_p2p(h->stream, h->d_rs_stage.p, h->d_maxd.p, h->LY.total, x.peers, h->opt.rank,
+                             h->opt.world_size, seq & 1, tag, x.xchg_slot, mode, x.d_xerr));
+        return LH_OK;
+    }
+    if (mode == 0) NCCLCHK(ncclAllReduce(h->d_maxd.p, h->d_maxd.p, 1, ncclFloat64, ncclMax, h->comm, h->stream));
+    NCCLCHK(ncclAllReduce(h->d_rs_stage.p, h->d_rs_stage.p, (size_t)h->LY.total, ncclFloat64, ncclSum, h->comm, h->stream));
     ++h->n_coll;
-    return lh_launch_p2p(h->stream, h->d_rs_stage.p, h->d_maxd.p, h->LY.total, h->peers, h->opt.rank, h->opt.world_size,
-                         seq & 1, tag, h->xchg_slot, mode, h->d_xerr);
+    return LH_OK;
+}
+
+// the per-chain exchange of a trial (mode 1) or of the initial linearisation (mode 0); *stopped as in enqueue_trial
+int exchange_chain(lh_handle* h, int mode, bool* stopped) {
+    switch (h->transport) {
+        case TR_NONE: break;
+        case TR_RCCL: case TR_P2P: { Prof pr(h, KC_ALLREDUCE); return exchange_on_stream(h, mode, false); }
+        case TR_HOST:
+            HIPCHK(hipStreamSynchronize(h->stream));
+            *stopped = mode != 0 && h->h_done[0];   // device-determined, identical on every rank
+            return *stopped ? LH_OK : host_exchange(h, mode);
+    }
+    return LH_OK;
 }
 
 // One LM trial (mode 1) or the initial linearisation (mode 0).  *stopped is set (host transport
@@ -962,23 +991,8 @@ int enqueue_trial(lh_handle* h, int mode, bool* stopped) {
                                 h->cur_trial, h->d_img.p));
         DBGSYNC("k_reduce");
     }
-    if (h->comm) {
-        Prof pr(h, KC_ALLREDUCE);
-        if (mode == 0) NCCLCHK(ncclAllReduce(h->d_maxd.p, h->d_maxd.p, 1, ncclFloat64, ncclMax, h->comm, s));
-        NCCLCHK(ncclAllReduce(h->d_rs_stage.p, h->d_rs_stage.p, (size_t)h->LY.total, ncclFloat64, ncclSum, h->comm, s));
-        ++h->n_coll;
-    } else if (h->p2p) {
-        Prof pr(h, KC_ALLREDUCE);
-        HIPCHK(p2p_exchange(h, mode, h->cur_trial));
-    } else if (h->host_comm) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (mode != 0 && h->h_done[0]) {   // device-determined, identical on every rank
-            *stopped = true;
-            return LH_OK;
-        }
-        int st = host_exchange(h, mode);
-        if (st != LH_OK) return st;
-    }
+    STAGE(exchange_chain(h, mode, stopped));
+    if (*stopped) return LH_OK;
     {
         Prof pr(h, KC_CTRL);
         if (h->cfg.kind == LH_CTRL_DENSE)
@@ -999,28 +1013,37 @@ bool wants_outliers(const lh_handle* h, const lh_result* out) {
     return out && h->opt.abi_version >= 5 && out->is_outlier != nullptr;
 }
 
-int download(lh_handle* h, lh_result* out, int cur) {
+// the outlier pass's three result scalars lie behind the flags (one copy brings both)
+size_t outlier_scalars_off(const lh_handle* h) { return ((size_t)h->O + 15) & ~(size_t)15; }
+void read_outlier_scalars(const lh_handle* h, lh_result* out) {
+    double r3[3];
+    std::memcpy(r3, h->s_oflag.p + outlier_scalars_off(h), sizeof(r3));
+    out->outlier_th = r3[0]; out->n_inlier = (int64_t)r3[1]; out->n_outlier = (int64_t)r3[2];
+}
+
+// Backend::Optimize's outlier pass on the device (backend_lego.cpp:163-194): flags + 3 scalars, into the pinned staging.
+// A sharded window: the reference counts the whole window's edges, so each rank counts its own, the five counts and the
+// edge counts are summed over the ranks (one 6-double exchange: every rank of the handle asks for the flags alike, as
+// it solves alike), and each rank flags its edges at the threshold the totals give.
+int outlier_pass(lh_handle* h, const lh_result* out) {
     hipStream_t s = h->stream;
-    const int P = h->P;
-    const double t0 = now_ms();
-    const size_t np = out->pose_Tcw ? 12 * (size_t)P : 0;
-    const size_t nl = (out->lm_xyz && h->L) ? 3 * (size_t)h->L : 0;
-    const size_t ne = (out->edge_robust_chi2 && h->O) ? (size_t)h->O : 0;
-    const bool fl = wants_outliers(h, out);
-    const size_t o_res = ((size_t)h->O + 15) & ~(size_t)15;   // the scalars behind the flags: one copy
-    if (fl) {   // Backend::Optimize's outlier pass on the device (backend_lego.cpp:163-194): flags + 3 scalars
-        HIPCHK(h->d_ocnt.ensure(5 * 256));
-        HIPCHK(h->d_oflag.ensure(o_res + 3 * sizeof(double)));
-        HIPCHK(h->s_oflag.ensure(o_res + 3 * sizeof(double)));
-        if (h->comm || h->host_comm) {
-            // a sharded window: the reference counts the whole window's edges, so each rank counts its own, the
-            // five counts and the edge counts are summed over the ranks (one 6-double exchange: every rank of the
-            // handle asks for the flags alike, as it solves alike), and each rank flags its edges at the
-            // threshold the totals give
+    const size_t bytes = outlier_scalars_off(h) + 3 * sizeof(double);
+    const double* rho = h->d_rho.p + h->rho_off;
+    const long nslots = (long)h->n_slots, n_obs = (long)h->O;
+    const double th = out->outlier_chi2_th;
+    HIPCHK(h->d_ocnt.ensure(5 * 256));
+    HIPCHK(h->d_oflag.ensure(bytes));
+    HIPCHK(h->s_oflag.ensure(bytes));
+    switch (h->transport) {
+        case TR_P2P:   // ADVICE.md, first finding: each rank thresholds on its own shard's counts.  The fix moves
+                       // this label down to the sharded cases (the sum through the caller's all-reduce).
+        case TR_NONE:
+            HIPCHK(lh_launch_outliers(s, rho, h->d_obs_perm.p, nslots, n_obs, th, h->d_ocnt.p, h->d_oflag.p));
+            break;
+        case TR_RCCL: case TR_HOST:
             HIPCHK(h->d_otot.ensure(6));
-            HIPCHK(lh_launch_outlier_counts(s, h->d_rho.p + h->rho_off, h->d_obs_perm.p, (long)h->n_slots, (long)h->O,
-                                            out->outlier_chi2_th, h->d_ocnt.p, h->d_otot.p));
-            if (h->comm) {
+            HIPCHK(lh_launch_outlier_counts(s, rho, h->d_obs_perm.p, nslots, n_obs, th, h->d_ocnt.p, h->d_otot.p));
+            if (h->transport == TR_RCCL) {
                 NCCLCHK(ncclAllReduce(h->d_otot.p, h->d_otot.p, 6, ncclFloat64, ncclSum, h->comm, s));
             } else {
                 double t6[6];
@@ -1030,27 +1053,30 @@ int download(lh_handle* h, lh_result* out, int cur) {
                 HIPCHK(hipMemcpyAsync(h->d_otot.p, t6, sizeof(t6), hipMemcpyHostToDevice, s));
                 HIPCHK(hipStreamSynchronize(s));   // (t6 is on this stack frame)
             }
-            HIPCHK(lh_launch_outlier_flags(s, h->d_rho.p + h->rho_off, h->d_obs_perm.p, (long)h->n_slots, (long)h->O,
-                                           out->outlier_chi2_th, h->d_otot.p, h->d_oflag.p));
-        } else {
-            HIPCHK(lh_launch_outliers(s, h->d_rho.p + h->rho_off, h->d_obs_perm.p, (long)h->n_slots, (long)h->O, out->outlier_chi2_th,
-                                      h->d_ocnt.p, h->d_oflag.p));
-        }
-        HIPCHK(hipMemcpyAsync(h->s_oflag.p, h->d_oflag.p, o_res + 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHK(lh_launch_outlier_flags(s, rho, h->d_obs_perm.p, nslots, n_obs, th, h->d_otot.p, h->d_oflag.p));
+            break;
     }
+    HIPCHK(hipMemcpyAsync(h->s_oflag.p, h->d_oflag.p, bytes, hipMemcpyDeviceToHost, s));
+    return LH_OK;
+}
+
+int download(lh_handle* h, lh_result* out, int cur) {
+    hipStream_t s = h->stream;
+    const int P = h->P;
+    const double t0 = now_ms();
+    const size_t np = out->pose_Tcw ? 12 * (size_t)P : 0;
+    const size_t nl = (out->lm_xyz && h->L) ? 3 * (size_t)h->L : 0;
+    const size_t ne = (out->edge_robust_chi2 && h->O) ? (size_t)h->O : 0;
+    const bool fl = wants_outliers(h, out);
+    if (fl) STAGE(outlier_pass(h, out));
     if (np + nl + ne == 0 && !fl) {
         out->time_download_ms = 0.0;
         return LH_OK;
     }
     if (np + nl + ne == 0) {
         HIPCHK(hipStreamSynchronize(s));
-        const uint8_t* sf = h->s_oflag.p;
-        double r3[3];
-        std::memcpy(r3, sf + o_res, sizeof(r3));
-        out->outlier_th = r3[0];
-        out->n_inlier = (int64_t)r3[1];
-        out->n_outlier = (int64_t)r3[2];
-        const ByteSeg seg_f = {out->is_outlier, sf, (size_t)h->O};
+        read_outlier_scalars(h, out);
+        const ByteSeg seg_f = {out->is_outlier, h->s_oflag.p, (size_t)h->O};
         par_copy(h, &seg_f, 1);
         out->time_download_ms = now_ms() - t0;
         return LH_OK;
@@ -1078,15 +1104,93 @@ int download(lh_handle* h, lh_result* out, int cur) {
     const ByteSeg seg_e[2] = {{out->edge_robust_chi2, st + np + nl, ne * sizeof(double)},
                               {fl ? out->is_outlier : nullptr, fl ? h->s_oflag.p : nullptr, fl ? (size_t)h->O : 0}};
     par_copy(h, seg_e, 2);
-    if (fl) {
-        double r3[3];
-        std::memcpy(r3, h->s_oflag.p + o_res, sizeof(r3));
-        out->outlier_th = r3[0];
-        out->n_inlier = (int64_t)r3[1];
-        out->n_outlier = (int64_t)r3[2];
-    }
+    if (fl) read_outlier_scalars(h, out);
     out->time_download_ms = now_ms() - t0;
     return LH_OK;
+}
+
+// ---- the stages of a resident solve.  Its start: the mapped words' reset, P2P's tag generation (every rank solves
+//      the same number of times); an exchange that failed earlier fails every later solve ----
+int begin_solve(lh_handle* h) {
+    volatile int* hd = h->h_done;   // [0] done, [1] progress word (ctrl_lm_step)
+    hd[0] = 0; hd[1] = -1;
+    h->n_coll = 0;
+    if (h->transport == TR_P2P) ++h->p2p.solve_gen;
+    return transport_failed(h) ? LH_E_RCCL : LH_OK;
+}
+
+// One turn of a host spin loop: every 4096th, and at most every 50 ms unless `often`, hipStreamQuery turns a device fault
+// or the transport's failure into an error return (a query delays the next launch by ~6 us).  idle: it found nothing queued.
+struct Watchdog { bool often = false, idle = false; unsigned spin = 0; double t_query = now_ms(); };
+int watchdog_turn(lh_handle* h, Watchdog& wd) {
+    wd.idle = false;
+    if ((++wd.spin & 4095) == 0 && (wd.often || now_ms() - wd.t_query > 50.0)) {
+        const hipError_t q = hipStreamQuery(h->stream);
+        if (q != hipSuccess && q != hipErrorNotReady) return LH_E_HIP;
+        if (transport_failed(h)) {
+            (void)hipStreamSynchronize(h->stream);
+            return LH_E_RCCL;
+        }
+        wd.idle = q == hipSuccess;
+        wd.t_query = now_ms();
+    }
+    __builtin_ia32_pause();
+    return LH_OK;
+}
+
+// The initial chain (its block 0 restarts the solve: controller, poses, tables, step; launch_lin), then the trials;
+// *enq: how many of those were enqueued.
+int enqueue_chains(lh_handle* h, const lh::TrialSchedule& ts, int* enq) {
+    volatile int* hd = h->h_done;
+    bool stopped = false;
+    STAGE(enqueue_trial(h, 0, &stopped));
+    if (exchange_synchronous(h)) {
+        // each trial's exchange waits for the previous k_ctrl, whose stop flag every rank reads at the same point
+        while (*enq < ts.max_total && !stopped) {
+            STAGE(enqueue_trial(h, 1, &stopped));
+            if (!stopped) ++*enq;
+        }
+        return LH_OK;
+    }
+    // k_ctrl writes each live trial it has decided into the mapped progress word; the host keeps ts.depth trials
+    // enqueued past it (one when the next iteration reaches max_iters: lh::may_enqueue) until the device raises done
+    static const bool query_often = getenv("LH_QUERY_OFTEN") != nullptr;   // diagnostic A/B switch (timing only)
+    Watchdog wd{query_often};
+    while (!hd[0] && *enq < ts.max_total) {
+        if (lh::may_enqueue(ts, hd[1], *enq)) {
+            STAGE(enqueue_trial(h, 1, &stopped));
+            ++*enq;
+        } else {
+            STAGE(watchdog_turn(h, wd));
+        }
+    }
+    return LH_OK;
+}
+
+// The top-up after the stop, to equal collective counts: no rank enqueued more than the schedule's target for the
+// stop chain and every rank tops up to it (lh_plan.h); nobody reads what these exchanges carry
+int exchange_top_up(lh_handle* h, const lh::TrialSchedule& ts, int enq, int stop_chain) {
+    if (!sharded(h) || exchange_synchronous(h)) return LH_OK;   // (synchronous: none was enqueued past the stop)
+    const int target = lh::topup_target(ts, stop_chain);
+    if (enq > target) return LH_E_STATE;   // cannot happen: the schedule's bound
+    for (; enq < target; ++enq) STAGE(exchange_on_stream(h, 1, true));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return transport_failed(h) ? LH_E_RCCL : LH_OK;
+}
+
+// the solve's summary from the controller's words (lh_ctrl, or the mapped lh_host_words)
+template <typename W>
+void write_summary(const lh_handle* h, const W& w, double time_ms, lh_result* out) {
+    out->time_ms = time_ms;
+    out->iterations = w.iter; out->trials = w.trials; out->accepted = w.accepted;
+    out->chi2_initial = w.chi2_initial; out->chi2_final = w.chi; out->lambda_final = w.lambda;
+    out->pcg_iterations = w.pcg_iters; out->degenerate = w.nonpd;
+    out->trace_len = std::min((int)w.trace_len, std::min(out->trace_cap, LH_TRACE));
+    for (int i = 0; i < out->trace_len; ++i) {
+        if (out->trace_chi2) out->trace_chi2[i] = w.trace_chi[i];
+        if (out->trace_lambda) out->trace_lambda[i] = w.trace_lambda[i];
+    }
+    out->time_prep_ms = h->last_prep_ms; out->time_upload_ms = h->last_upload_ms; out->time_download_ms = 0.0;
 }
 
 int solve_resident_impl(lh_handle* h, lh_result* out) {
@@ -1094,154 +1198,44 @@ int solve_resident_impl(lh_handle* h, lh_result* out) {
     hipStream_t s = h->stream;
     hipEvent_t e0 = next_event(h), e1 = next_event(h);
     if (!e0 || !e1) return LH_E_HIP;
-    volatile int* hd = h->h_done;   // [0] done, [1] progress word (ctrl_lm_step)
-    hd[0] = 0;
-    hd[1] = -1;
     // No arrays wanted (and no collectives, profiling or printout): the summary comes with done in the
     // mapped words, and the solve returns when the host sees it; later work on this handle is stream-
     // ordered behind the solve's kernels (lh_destroy synchronises)
     const bool fast = out && !out->pose_Tcw && !out->lm_xyz && !out->edge_robust_chi2 && !wants_outliers(h, out) &&
-                      !h->comm && !h->host_comm && !h->p2p && !h->opt.profile && !h->opt.verbose;
+                      !sharded(h) && !h->opt.profile && !h->opt.verbose;
+    const lh::TrialSchedule ts = lh::trial_schedule(h->opt.max_iters, h->opt.max_trials, h->prm.eval_first,
+                                                    h->opt.trials_per_sync, exchange_synchronous(h));
     const double t_start = now_ms();
-    h->n_coll = 0;
-    if (h->p2p) {
-        ++h->solve_gen;   // every rank solves the same number of times
-        if (*h->h_xerr) return LH_E_RCCL;   // an earlier exchange failed: the peers are not in step
-    }
+    STAGE(begin_solve(h));
     if (!fast) HIPCHK(hipEventRecord(e0, s));   // (the array-free solve times itself on the host clock)
-    // (the restart -- controller, poses, tables, step -- is the initial linearisation's block 0, launch_lin)
-    bool stopped = false;
-    int st = enqueue_trial(h, 0, &stopped);
-    if (st != LH_OK) return st;
-    // every trial, plus one re-linearisation chain per iteration at most (an evaluate-only acceptance, ctrl.relin)
-    const int max_total = (h->opt.max_iters > 0) ? h->opt.max_iters * (std::max(1, h->opt.max_trials) + (h->prm.eval_first ? 1 : 0)) : 0;
-    const int depth = h->host_comm ? 1 : (h->opt.trials_per_sync > 0 ? std::min(h->opt.trials_per_sync, 32) : 2);
     int enq = 0;
-    if (h->host_comm) {
-        // synchronous: each trial's exchange waits for the previous k_ctrl, whose stop flag every
-        // rank reads at the same point
-        while (enq < max_total && !stopped) {
-            if ((st = enqueue_trial(h, 1, &stopped)) != LH_OK) return st;
-            if (!stopped) ++enq;
-        }
-    } else {
-        // k_ctrl writes each live trial it has decided into the mapped progress word; the host
-        // keeps `depth` trials enqueued past it (one when the next completed iteration reaches
-        // max_iters) until the device raises done.  hipStreamQuery at most every 50 ms turns a
-        // device fault into an error return (each query delays the next launch by ~6 us).
-        unsigned spin = 0;
-        static const bool query_often = getenv("LH_QUERY_OFTEN") != nullptr;   // diagnostic A/B switch (timing only)
-        double t_query = now_ms();
-        while (!hd[0] && enq < max_total) {
-            const int pw = hd[1];   // 2 * (last live trial) + near, or -1 before the first
-            const int last = pw < 0 ? -1 : (pw >> 1);
-            if (enq - last < ((pw >= 0 && (pw & 1)) ? 1 : depth)) {
-                if ((st = enqueue_trial(h, 1, &stopped)) != LH_OK) return st;
-                ++enq;
-                continue;
-            }
-            if ((++spin & 4095) == 0 && (query_often || now_ms() - t_query > 50.0)) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q != hipSuccess && q != hipErrorNotReady) return LH_E_HIP;
-                if (h->p2p && *h->h_xerr) {   // a peer's tag did not arrive (k_p2p_sum gave up)
-                    (void)hipStreamSynchronize(s);
-                    return LH_E_RCCL;
-                }
-                t_query = now_ms();
-            }
-            __builtin_ia32_pause();
-        }
-    }
+    STAGE(enqueue_chains(h, ts, &enq));
     if (fast) {
-        // every trial is enqueued: the device raises done on the last one (max_iters x max_trials trials
-        // reach max_iters); a fault, or an idle stream without done, ends the wait with an error
-        double t_query = now_ms();
-        unsigned spin = 0;
-        while (!hd[0]) {
-            if ((++spin & 4095) == 0 && now_ms() - t_query > 50.0) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipSuccess && !hd[0]) return LH_E_STATE;
-                if (q != hipSuccess && q != hipErrorNotReady) return LH_E_HIP;
-                t_query = now_ms();
-            }
-            __builtin_ia32_pause();
+        // the wait: every trial is enqueued and done comes with the last; a fault, or an idle stream without it, ends it
+        volatile int* hd = h->h_done;
+        for (Watchdog wd; !hd[0];) {
+            STAGE(watchdog_turn(h, wd));
+            if (wd.idle && !hd[0]) return LH_E_STATE;
         }
         std::atomic_thread_fence(std::memory_order_acquire);
-        const volatile lh_host_words* hw = reinterpret_cast<const volatile lh_host_words*>(h->h_done);
-        out->iterations = hw->iter;
-        out->trials = hw->trials;
-        out->accepted = hw->accepted;
-        out->chi2_initial = hw->chi2_initial;
-        out->chi2_final = hw->chi;
-        out->lambda_final = hw->lambda;
-        out->time_ms = now_ms() - t_start;   // host clock: enqueue of the first kernel to done seen
-        out->pcg_iterations = hw->pcg_iters;
-        out->degenerate = hw->nonpd;
-        out->trace_len = std::min((int)hw->trace_len, std::min(out->trace_cap, LH_TRACE));
-        for (int i = 0; i < out->trace_len; ++i) {
-            if (out->trace_chi2) out->trace_chi2[i] = hw->trace_chi[i];
-            if (out->trace_lambda) out->trace_lambda[i] = hw->trace_lambda[i];
-        }
-        out->time_prep_ms = h->last_prep_ms;
-        out->time_upload_ms = h->last_upload_ms;
-        out->time_download_ms = 0.0;
-        h->event_next = 0;
-        h->last_chains = -1;   // (not in the host words)
-        h->last_lskips = -1;
+        const double ms = now_ms() - t_start;   // host clock: enqueue of the first kernel to done seen
+        write_summary(h, *reinterpret_cast<const volatile lh_host_words*>(h->h_done), ms, out);
+        h->event_next = 0; h->last_chains = h->last_lskips = -1;   // (the chain counts are not in the host words)
         return LH_OK;
     }
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipMemcpyAsync(h->h_ctrl, h->d_ctrl.p, sizeof(lh_ctrl), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const lh_ctrl& c = *h->h_ctrl;
-    if (h->comm || h->p2p) {
-        // Equal collective counts on every rank.  The progress word only advances on live chains,
-        // so no rank enqueued more than (stop chain) + depth chains; the stop chain is decided by
-        // identical all-reduced data, so every rank tops up to the same target.  The extra
-        // all-reduces carry no data anyone reads (the device has stopped).
-        const int target = std::min(c.seq_last + depth, max_total);
-        if (enq > target) return LH_E_STATE;   // cannot happen: the bound above
-        for (; enq < target; ++enq) {
-            if (h->p2p) {
-                HIPCHK(p2p_exchange(h, 1, ++h->cur_trial));   // the chain numbers continue as the trials' did
-            } else {
-                NCCLCHK(ncclAllReduce(h->d_rs_stage.p, h->d_rs_stage.p, (size_t)h->LY.total, ncclFloat64, ncclSum, h->comm, s));
-                ++h->n_coll;
-            }
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        if (h->p2p && *h->h_xerr) return LH_E_RCCL;
-    }
+    STAGE(exchange_top_up(h, ts, enq, c.seq_last));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    const int cur = c.cur;
     h->rho_off = (size_t)c.rho_sel * h->n_slots;
-    h->last_batches = c.nbatches;
-    h->last_retrials[0] = c.nretrials[0];
-    h->last_retrials[1] = c.nretrials[1];
-    h->last_chains = c.seq_last;
-    h->last_lskips = c.lskips;
-
+    h->last_batches = c.nbatches; h->last_retrials[0] = c.nretrials[0]; h->last_retrials[1] = c.nretrials[1];
+    h->last_chains = c.seq_last; h->last_lskips = c.lskips;
     if (out) {
-        out->iterations = c.iter;
-        out->trials = c.trials;
-        out->accepted = c.accepted;
-        out->chi2_initial = c.chi2_initial;
-        out->chi2_final = c.chi;
-        out->lambda_final = c.lambda;
-        out->time_ms = ms;
-        out->pcg_iterations = c.pcg_iters;
-        out->degenerate = c.nonpd;
-        out->trace_len = std::min(c.trace_len, std::min(out->trace_cap, LH_TRACE));
-        for (int i = 0; i < out->trace_len; ++i) {
-            if (out->trace_chi2) out->trace_chi2[i] = c.trace_chi[i];
-            if (out->trace_lambda) out->trace_lambda[i] = c.trace_lambda[i];
-        }
-        out->time_prep_ms = h->last_prep_ms;
-        out->time_upload_ms = h->last_upload_ms;
-        out->time_download_ms = 0.0;
-        st = download(h, out, cur);
-        if (st != LH_OK) return st;
+        write_summary(h, c, ms, out);
+        STAGE(download(h, out, c.cur));
     }
     if (h->opt.verbose) {
         printf("==========LEGO OPTIMIZER (MI355X)==========\n");
@@ -1256,57 +1250,64 @@ int solve_resident_impl(lh_handle* h, lh_result* out) {
 
 // Every rank must run the same controller with the same options: the LM decisions are taken on
 // identical all-reduced sums, and the number of collectives a solve issues is a function of the stop
-// trial, the enqueue depth and max_iters x max_trials (solve_resident_impl).  Ranks whose options
+// trial, the enqueue depth and max_iters x max_trials (lh_plan.h trial_schedule).  Ranks whose options
 // differ would issue different collective counts and hang, so lh_create compares them once: each
 // rank contributes (v, -v) per option to a MAX all-reduce, and any rank whose v differs from the
 // maximum or minimum sees a mismatch (every rank returns LH_E_BADARG).
-// MAX over the ranks of buf[0..n), in place (host transport or RCCL); a no-op on one rank
+// MAX over the ranks of buf[0..n), in place; a no-op on one rank
 int rank_max(lh_handle* h, double* buf, int n) {
-    if (h->host_comm || h->p2p) {
-        if (h->opt.allreduce(h->opt.allreduce_user, buf, n, 1) != 0) return LH_E_RCCL;
-    } else if (h->comm) {
-        DevBuf<double> d;
-        auto run = [&]() -> int {
-            HIPCHK(d.ensure(n));
-            HIPCHK(hipMemcpyAsync(d.p, buf, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            NCCLCHK(ncclAllReduce(d.p, d.p, n, ncclFloat64, ncclMax, h->comm, h->stream));
-            HIPCHK(hipMemcpyAsync(buf, d.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            return LH_OK;
-        };
-        const int st = run();
-        d.release();
-        return st;
+    switch (h->transport) {
+        case TR_NONE: return LH_OK;
+        case TR_HOST: case TR_P2P: return h->opt.allreduce(h->opt.allreduce_user, buf, n, 1) != 0 ? LH_E_RCCL : LH_OK;
+        case TR_RCCL: break;
     }
-    return LH_OK;
+    DevBuf<double> d;
+    auto run = [&]() -> int {
+        HIPCHK(d.ensure(n));
+        HIPCHK(hipMemcpyAsync(d.p, buf, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        NCCLCHK(ncclAllReduce(d.p, d.p, n, ncclFloat64, ncclMax, h->comm, h->stream));
+        HIPCHK(hipMemcpyAsync(buf, d.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return LH_OK;
+    };
+    const int st = run();
+    d.release();
+    return st;
+}
+
+// every peer's mapping closed (this rank's own entry is its buffer, not a mapping)
+void p2p_close_peers(P2pState& x) {
+    for (int r = 0; r < LH_P2P_MAX; ++r)
+        if (x.peers.p[r] && x.peers.p[r] != x.d_xchg.p) (void)hipIpcCloseMemHandle(x.peers.p[r]);
+    x.peers = lh_peers{};
 }
 
 // P2P: this rank's exchange buffer (2 parities x world slots of the packed reduced system + max|diag H_ll|, then
 // the arrival tags), exported over IPC, and every peer's opened here.  Collective: every rank calls it at the same
 // upload (the buffer size follows from the reduced system's layout, identical on every rank); its handles travel
 // through the caller's all-reduce (a sum of byte values, exact), and a MAX all-reduce of the status ends it, so a
-// rank that cannot map a peer takes every rank's upload down with it.
+// rank that cannot map a peer takes every rank's upload down with it.  The other transports have no such buffers.
 int p2p_setup(lh_handle* h) {
+    if (h->transport != TR_P2P) return LH_OK;
+    P2pState& x = h->p2p;
     const int world = h->opt.world_size, rank = h->opt.rank;
     const long slot = (h->LY.total + 1 + 63) & ~63L;
     const size_t need = (size_t)2 * world * slot + 2 * (size_t)world;   // (a tag is one 8-byte word)
-    if (h->d_xchg.n >= need && h->xchg_slot == slot) return LH_OK;
+    if (x.d_xchg.n >= need && x.xchg_slot == slot) return LH_OK;
     int st = LH_OK;
-    for (int r = 0; r < world; ++r)
-        if (r != rank && h->peers.p[r]) (void)hipIpcCloseMemHandle(h->peers.p[r]);
-    h->peers = lh_peers{};
-    h->d_xchg.release();
+    p2p_close_peers(x);
+    x.d_xchg.release();
     hipIpcMemHandle_t mine{};
-    if (h->d_xchg.ensure(need) != hipSuccess ||
-        hipMemsetAsync(h->d_xchg.p, 0, need * sizeof(double), h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess || hipIpcGetMemHandle(&mine, h->d_xchg.p) != hipSuccess)
+    if (x.d_xchg.ensure(need) != hipSuccess ||
+        hipMemsetAsync(x.d_xchg.p, 0, need * sizeof(double), h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess || hipIpcGetMemHandle(&mine, x.d_xchg.p) != hipSuccess)
         st = LH_E_HIP;
     static_assert(sizeof(hipIpcMemHandle_t) <= 64, "an IPC handle in 64 byte values");
     std::vector<double> hb((size_t)world * 64, 0.0);
     const uint8_t* mb = reinterpret_cast<const uint8_t*>(&mine);
     for (size_t i = 0; i < sizeof(mine); ++i) hb[(size_t)rank * 64 + i] = (double)mb[i];
     if (h->opt.allreduce(h->opt.allreduce_user, hb.data(), (int64_t)hb.size(), 0) != 0) return LH_E_RCCL;
-    h->peers.p[rank] = h->d_xchg.p;
+    x.peers.p[rank] = x.d_xchg.p;
     for (int r = 0; r < world && st == LH_OK; ++r) {
         if (r == rank) continue;
         hipIpcMemHandle_t ph{};
@@ -1317,20 +1318,20 @@ int p2p_setup(lh_handle* h) {
             if (getenv("LH_DEBUG_P2P")) fprintf(stderr, "lego_ba: rank %d cannot map rank %d's exchange buffer\n", rank, r);
             st = LH_E_UNSUPPORTED;
         } else {
-            h->peers.p[r] = static_cast<double*>(p);
+            x.peers.p[r] = static_cast<double*>(p);
         }
     }
     double fs = (double)st;
     const int st_r = rank_max(h, &fs, 1);
     if (st_r != LH_OK) return st_r;
     if (fs > 0.0) return (int)fs;
-    h->xchg_slot = slot;
+    x.xchg_slot = slot;
     return LH_OK;
 }
 
 int check_rank_options(lh_handle* h) {
     const lh_options& o = h->opt;
-    const int depth = h->host_comm ? 1 : (o.trials_per_sync > 0 ? std::min(o.trials_per_sync, 32) : 2);
+    const int depth = lh::trial_schedule(o.max_iters, o.max_trials, 0, o.trials_per_sync, exchange_synchronous(h)).depth;
     const double v[] = {(double)o.max_iters, (double)o.max_trials, (double)o.strategy, o.huber_delta, o.stop_dchi2,
                         o.tau, o.lambda_cap, o.lambda_init, (double)o.linear_solver, (double)o.world_size,
                         (double)o.degenerate_guard, (double)depth, (double)o.pcg_max_iters, o.pcg_tol,
@@ -1339,7 +1340,7 @@ int check_rank_options(lh_handle* h) {
     constexpr int n = (int)(sizeof(v) / sizeof(v[0]));
     double buf[2 * n];
     for (int i = 0; i < n; ++i) { buf[i] = v[i]; buf[n + i] = -v[i]; }
-    if (!h->host_comm && !h->comm && !h->p2p) return LH_OK;
+    if (!sharded(h)) return LH_OK;
     const int st = rank_max(h, buf, 2 * n);
     if (st != LH_OK) return st;
     for (int i = 0; i < n; ++i)
@@ -1463,21 +1464,21 @@ int lh_create(lh_handle** hp, const lh_options* opt) {
         lh_destroy(h);
         return LH_E_HIP;
     }
-    h->host_comm = opt->world_size > 1 && opt->comm_mode == LH_COMM_HOST;
-    h->p2p = opt->world_size > 1 && opt->comm_mode == LH_COMM_P2P;
-    if (h->p2p) {
-        if (hipHostMalloc((void**)&h->h_xerr, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&h->d_xerr, h->h_xerr, 0) != hipSuccess) {
-            lh_destroy(h);
-            return LH_E_HIP;
-        }
-        *h->h_xerr = 0;
-    }
-    // LH_FORCE_RCCL=1 builds a one-rank communicator on a single GPU, so the data-path
+    // The transport.  LH_FORCE_RCCL=1 builds a one-rank communicator on a single GPU, so the data-path
     // collectives (and their stream ordering) run in single-GPU tests too
     const char* force = std::getenv("LH_FORCE_RCCL");
     const bool force_comm = opt->world_size == 1 && force && force[0] == '1';
-    if ((opt->world_size > 1 && !h->host_comm && !h->p2p) || force_comm) {
+    h->transport = opt->world_size == 1 ? (force_comm ? TR_RCCL : TR_NONE)
+                 : opt->comm_mode == LH_COMM_HOST ? TR_HOST : opt->comm_mode == LH_COMM_P2P ? TR_P2P : TR_RCCL;
+    if (h->transport == TR_P2P) {
+        if (hipHostMalloc((void**)&h->p2p.h_xerr, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+            hipHostGetDevicePointer((void**)&h->p2p.d_xerr, h->p2p.h_xerr, 0) != hipSuccess) {
+            lh_destroy(h);
+            return LH_E_HIP;
+        }
+        *h->p2p.h_xerr = 0;
+    }
+    if (h->transport == TR_RCCL) {
         ncclUniqueId id;
         if (force_comm) {
             if (ncclGetUniqueId(&id) != ncclSuccess) { lh_destroy(h); return LH_E_RCCL; }
@@ -1503,10 +1504,8 @@ void lh_destroy(lh_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm) ncclCommDestroy(h->comm);
-    for (int r = 0; r < LH_P2P_MAX; ++r)
-        if (h->peers.p[r] && h->peers.p[r] != h->d_xchg.p) (void)hipIpcCloseMemHandle(h->peers.p[r]);
-    h->d_xchg.release();
-    if (h->h_xerr) (void)hipHostFree(h->h_xerr);
+    p2p_close_peers(h->p2p); h->p2p.d_xchg.release();
+    if (h->p2p.h_xerr) (void)hipHostFree(h->p2p.h_xerr);
     for (auto e : h->event_pool) (void)hipEventDestroy(e);
     delete h->pool;
     h->f_in.release(); h->f_out.release(); h->f_res.release(); h->s_fin.release(); h->s_fout.release();

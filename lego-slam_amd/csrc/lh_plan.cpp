@@ -872,6 +872,15 @@ int solve_config(const SolveIn& in, SolveConfig& c) {
     return LH_OK;
 }
 
+TrialSchedule trial_schedule(int max_iters, int max_trials, int eval_first, int trials_per_sync, bool host_transport) {
+    TrialSchedule ts;
+    ts.max_total = (max_iters > 0) ? max_iters * (std::max(1, max_trials) + (eval_first ? 1 : 0)) : 0;
+    ts.depth = host_transport ? 1 : (trials_per_sync > 0 ? std::min(trials_per_sync, 32) : 2);
+    return ts;
+}
+
+int topup_target(const TrialSchedule& ts, int stop_chain) { return std::min(stop_chain + ts.depth, ts.max_total); }
+
 bool reduce_skip(int world_size, const Switches& sw) { return world_size == 1 && !sw.no_red_skip; }
 
 int reduce_table(const Plan& pl, bool skip, uint32_t* rt) {

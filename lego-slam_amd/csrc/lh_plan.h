@@ -202,6 +202,31 @@ struct SolveConfig {
 // LH_OK, or LH_E_UNSUPPORTED: LDL^T past LH_PMAX_WIN poses on a window that cannot run banded
 int solve_config(const SolveIn& in, SolveConfig& out);
 
+// ---------------------------------------------------------------------------------------------
+// The trial schedule of a solve: how many chains the host may enqueue, and how far ahead of the
+// device.  lh_host.cpp's enqueue loop, its top-up and lh_create's option comparison all read it here.
+// With more than one rank every rank must issue the same number of exchanges per solve:
+//   * the progress word (2 * last live chain + near) only advances on live chains, so it never passes
+//     the stop chain s, and may_enqueue keeps a rank's count within s + depth;
+//   * s is decided on identical all-reduced data, so every rank tops up to the same topup_target(s).
+// tests/test_trial_schedule_cpu.py checks both by simulation.
+// ---------------------------------------------------------------------------------------------
+struct TrialSchedule {
+    int max_total;   // trials a solve can run: every trial, plus one re-linearisation chain per iteration at most
+                     // (an evaluate-only acceptance, ctrl.relin)
+    int depth;       // trials kept enqueued past the progress word (1: the synchronous host transport)
+};
+TrialSchedule trial_schedule(int max_iters, int max_trials, int eval_first, int trials_per_sync, bool host_transport);
+// May one more trial be enqueued, `enqueued` being out already?  progress: the mapped progress word, -1
+// before the first decision; its low bit (the next completed iteration reaches max_iters) allows one ahead.
+// (inline: the enqueue loop spins on it)
+inline bool may_enqueue(const TrialSchedule& ts, int progress, int enqueued) {
+    const int last = progress < 0 ? -1 : (progress >> 1);
+    return enqueued - last < ((progress >= 0 && (progress & 1)) ? 1 : ts.depth);
+}
+// The count every rank reaches after the device stopped on chain stop_chain (lh_ctrl.seq_last)
+int topup_target(const TrialSchedule& ts, int stop_chain);
+
 // k_reduce's blocks, one per pose pair that some chunk's rows reach ({block, first row, end row, p | q << 16}),
 // then the scalar block's sentinel, into out[4 (npairs + 1)].  One rank skips the pairs no chunk couples:
 // their blocks of S are zero for the whole window (the caller clears the reduced-system buffers per

@@ -145,6 +145,20 @@ int lhp_solve_config(const lh_window* w, int linear_solver, int max_trials, int 
     return LH_OK;
 }
 
+// The trial schedule (lh_plan.h trial_schedule, may_enqueue, topup_target) for tests: out2 = {max_total, depth}
+void lhp_trial_schedule(int max_iters, int max_trials, int eval_first, int trials_per_sync, int host_transport,
+                        int32_t* out2) {
+    const lh::TrialSchedule ts = lh::trial_schedule(max_iters, max_trials, eval_first, trials_per_sync, host_transport != 0);
+    out2[0] = ts.max_total;
+    out2[1] = ts.depth;
+}
+int lhp_may_enqueue(int max_total, int depth, int progress, int enqueued) {
+    return lh::may_enqueue(lh::TrialSchedule{max_total, depth}, progress, enqueued) ? 1 : 0;
+}
+int lhp_topup_target(int max_total, int depth, int stop_chain) {
+    return lh::topup_target(lh::TrialSchedule{max_total, depth}, stop_chain);
+}
+
 // k_reduce's block table of window `w` (reduce_table; the skip rule from world_size and the environment):
 // table [4 (npairs + 1)], *n_blocks the pair blocks listed.  Returns the lh_status.
 int lhp_reduce_table(const lh_window* w, int world_size, uint32_t* table, int32_t* n_blocks) {

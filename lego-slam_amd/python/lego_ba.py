@@ -604,6 +604,10 @@ def _pl():
         lib.lhp_ctrl_nd.argtypes = [C.c_int, vp, vp, vp, vp]
         lib.lhp_solve_config.argtypes = [C.POINTER(LhWindow), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
         lib.lhp_reduce_table.argtypes = [C.POINTER(LhWindow), C.c_int, vp, vp]
+        lib.lhp_trial_schedule.argtypes = [C.c_int] * 5 + [vp]
+        lib.lhp_trial_schedule.restype = None
+        lib.lhp_may_enqueue.argtypes = [C.c_int] * 4
+        lib.lhp_topup_target.argtypes = [C.c_int] * 3
         lib.lhp_pool_stress.restype = C.c_int64
         _planlib = lib
     return _planlib
@@ -682,6 +686,24 @@ def reduce_table(w, world_size=1):
     n = np.zeros(1, np.int32)
     _check(_pl().lhp_reduce_table(C.byref(ref.s), int(world_size), _ptr(tab), _ptr(n)), "lhp_reduce_table")
     return tab.reshape(-1, 4)[:int(n[0]) + 1], npairs, pw["pair_ptr"]
+
+
+def trial_schedule(max_iters, max_trials, eval_first, trials_per_sync, host_transport):
+    """(max_total, depth) of a solve with these options (lh_plan.h trial_schedule)."""
+    v = np.zeros(2, np.int32)
+    _pl().lhp_trial_schedule(int(max_iters), int(max_trials), int(eval_first), int(trials_per_sync),
+                             int(bool(host_transport)), _ptr(v))
+    return int(v[0]), int(v[1])
+
+
+def may_enqueue(max_total, depth, progress, enqueued):
+    """lh_plan.h may_enqueue: the enqueue loop's test, given the progress word and the count enqueued."""
+    return bool(_pl().lhp_may_enqueue(int(max_total), int(depth), int(progress), int(enqueued)))
+
+
+def topup_target(max_total, depth, stop_chain):
+    """lh_plan.h topup_target: the count every rank reaches after the device stopped on stop_chain."""
+    return int(_pl().lhp_topup_target(int(max_total), int(depth), int(stop_chain)))
 
 
 def pool_stress(threads, runs, n):
