@@ -21,6 +21,9 @@
  *                                                                  or lh_classify_outliers (host, on edge_robust_chi2)
  *     Frontend::EstimateCurrentPose frontend_lego.cpp:157-250 lh_estimate_pose (batched)
  *     LKOpticalFlow4Layer / 1Layer  algorithm.cpp:11-206      lh_lk_track
+ *     triangulation                 algorithm.h:11-34         lh_triangulate (batched)
+ *     Frontend::TriangulateNewPoints frontend_lego.cpp:111-155 lh_stereo_landmarks (LK left -> right + triangulation,
+ *     Frontend::BuildInitMap        frontend_lego.cpp:323-362                       one call per stereo frame)
  *     ~Problem                     problem.cpp:32 lh_destroy
  *
  * Plain C types only (no torch, Eigen or Sophus in any signature).  No C++
@@ -298,6 +301,81 @@ typedef struct lh_lk_result {
 } lh_lk_result;
 
 int lh_lk_track(lh_handle *h, const lh_lk_input *in, lh_lk_result *out);
+
+/*
+ * Batched SVD triangulation, replacing
+ *   bool triangulation(const std::vector<SE3> &poses, const VecVec3 &points, Vec3 &pt_world,
+ *                      double singRatioThr = 1e-3)                  (include/legoslam/algorithm.h:11-34)
+ * as Frontend::TriangulateNewPoints (src/frontend_lego.cpp:111-155) and Frontend::BuildInitMap (:323-362) call it
+ * once per stereo feature.  Per point: two rows of A per view, x m.row(2) - m.row(0) and y m.row(2) - m.row(1)
+ * (:18-22), with (x, y) the view's normalised camera coordinates (Camera::pixel2camera at depth 1,
+ * src/camera.cpp:21-25, when cam_K is given); the right singular vector v of A's smallest singular value;
+ * pt = v[0..2] / v[3] (:24).  One lane per point in fp64; a point's result depends on nothing but its own views
+ * (the same bits at any batch position and batch size).  Any number (>= 2) of views per point.
+ *
+ * flags, 0 = accepted:
+ *   bit 0  a component of pt is NaN or infinite                       algorithm.h:26-28
+ *   bit 1  !(sigma3 / sigma2 < sing_ratio_thr)                        algorithm.h:30-33
+ *          (a NaN ratio fails, as in the reference; the ratio is NaN when sigma2 <= 4 eps sigma0, i.e. A has two
+ *          null directions to working precision, as with two identical views: the reference's quotient of two
+ *          rounding-noise values is replaced by a definite rejection)
+ *   bit 2  gate: !(pt[1] <= y_max)                                    frontend_lego.cpp:134
+ *   bit 3  gate: !(pt[2] > z_min && pt[2] <= z_max)                   frontend_lego.cpp:135
+ *   bit 4  lh_stereo_landmarks: the LK track failed; the point is not triangulated (pt = 0)
+ * Every test is evaluated (the reference stops at its first failure, so a rejected point may carry several bits),
+ * the gate on pt before T_out.  With T_out and flags == 0, pt <- T_out * pt (current_pose_Twc * pworld, :138);
+ * a rejected point keeps its untransformed value.
+ *
+ * LH_E_BADARG: a null required pointer, a point with fewer than 2 views (the reference would read V.col(3) of a
+ * 2x4 system), a pose index out of range, a view_ptr that does not start at >= 0 or decreases.  n_points == 0: LH_OK.
+ */
+typedef struct lh_tri_input {
+    int32_t n_points;
+    int32_t n_poses;
+    const double *pose_Tcw;     /* [n_poses][12] row-major [R|t]: Camera::pose() of each view's camera (or any SE3) */
+    const double *cam_K;        /* [n_poses][4] fx,fy,cx,cy: view_xy holds pixels; NULL: already normalised */
+    const int64_t *view_ptr;    /* [n_points+1] CSR over views; NULL: every point has n_poses views, view v uses pose v */
+    const uint32_t *view_pose;  /* [n_views] pose index (ignored when view_ptr is NULL) */
+    const double *view_xy;      /* [n_views][2] */
+    double sing_ratio_thr;      /* singRatioThr = 1e-3, algorithm.h:14 */
+    int32_t gate;               /* 1: apply y_max / z_min / z_max (frontend_lego.cpp:133-136) */
+    double y_max, z_min, z_max;
+    const double *T_out;        /* [12] or NULL */
+} lh_tri_input;
+typedef struct lh_tri_result {
+    double *pt;                 /* [n_points][3] */
+    uint8_t *flags;             /* [n_points] 0 = accepted; bits as above */
+    double *sing_ratio;         /* [n_points] sigma3/sigma2, or NULL */
+    int32_t n_accepted;
+    double time_ms;             /* device time, copies excluded */
+} lh_tri_result;
+int lh_triangulate(lh_handle *h, const lh_tri_input *in, lh_tri_result *out);
+
+/*
+ * One stereo frame's new landmarks without a host round trip: lh_lk_track from the left image (lk.img1, lk.kp1)
+ * to the right (lk.img2), then lh_triangulate on every tracked pair, reading kp1 and kp2 on the device (floats
+ * widened to double, as toVec2 does, algorithm.h:37).  View 0 is the left camera (pose_Tcw[0], cam_K[0]), view 1
+ * the right.  kp2 and success are bitwise lh_lk_track's; pt and flags are bitwise lh_triangulate's on them; a point
+ * whose track failed carries flag bit 4 alone.  out->kp2 holds the initial guess when lk.has_initial.
+ */
+typedef struct lh_stereo_input {
+    lh_lk_input lk;             /* img1 = left, img2 = right */
+    const double *pose_Tcw;     /* [2][12] camera_left_->pose(), camera_right_->pose() */
+    const double *cam_K;        /* [2][4] fx,fy,cx,cy of the two cameras; NULL: the keypoints are already normalised */
+    double sing_ratio_thr;
+    int32_t gate;
+    double y_max, z_min, z_max;
+    const double *T_out;        /* [12] or NULL */
+} lh_stereo_input;
+typedef struct lh_stereo_result {
+    float *kp2;                 /* [n_points][2] */
+    uint8_t *success;           /* [n_points] */
+    double *pt;                 /* [n_points][3] */
+    uint8_t *flags;             /* [n_points] */
+    int32_t n_accepted;
+    double time_ms;             /* device time: pyramid + tracking + triangulation (copies excluded) */
+} lh_stereo_result;
+int lh_stereo_landmarks(lh_handle *h, const lh_stereo_input *in, lh_stereo_result *out);
 
 /* ---- test hooks (not part of the reference interface) ---- */
 /* f64 MFMA accumulator-layout probe: D(16x16) = A(16x4) * B(4x16), device pointers, row-major */

@@ -25,6 +25,7 @@
 #include "lh_common.h"
 #include "lh_lk.h"
 #include "lh_plan.h"
+#include "lh_tri.h"
 
 extern "C" {
 hipError_t lh_prepare_lin(int lds_limit);
@@ -71,6 +72,7 @@ hipError_t lh_launch_frames(hipStream_t st, int n_frames, const int64_t* obs_ptr
                             const double* pts, const double* uv, const uint8_t* flag_in, lh_params prm, double* res,
                             double* pose_out, uint8_t* flag_out, double* rchi2_out, int32_t* iters_out,
                             int32_t* inliers_out);
+hipError_t lh_launch_triangulate(hipStream_t st, const lh_tri_args* a);
 }
 
 namespace {
@@ -330,6 +332,8 @@ struct lh_handle {
     // LK optical flow (lh_lk_track): both images' pyramids, keypoints
     DevBuf<uint8_t> k_img[2], k_succ;
     DevBuf<float> k_kp1, k_kp2;
+    // triangulation (lh_triangulate, lh_stereo_landmarks): the inputs packed into one arena, the outputs into another
+    DevBuf<uint8_t> t_in, t_out;
     lh_ctrl* h_ctrl = nullptr;   // pinned
     int last_chains = -1;        // lh_debug_chains: the last synchronous solve's stop chain
     int last_lskips = -1;        // lh_debug_ladder: its rejections onto a built ladder rung
@@ -1510,6 +1514,7 @@ void lh_destroy(lh_handle* h) {
     delete h->pool;
     h->f_in.release(); h->f_out.release(); h->f_res.release(); h->s_fin.release(); h->s_fout.release();
     h->k_img[0].release(); h->k_img[1].release(); h->k_succ.release(); h->k_kp1.release(); h->k_kp2.release();
+    h->t_in.release(); h->t_out.release();
     h->d_chunks.release(); h->d_sbs.release(); h->d_meta.release(); h->d_obs_perm.release(); h->d_lm_perm.release();
     h->d_pair_ptr.release(); h->d_items.release(); h->d_pair_pq.release(); h->d_lm_in.release();
     h->d_uv.release(); h->d_rec.release(); h->d_ptab.release(); h->d_out_xyz.release(); h->d_out_rho.release();
@@ -1672,13 +1677,14 @@ static int estimate_pose_impl(lh_handle* h, const lh_frames* in, lh_frames_resul
 
 // LKOpticalFlow4Layer / LKOpticalFlow1Layer (algorithm.cpp:11-206): upload both images, build the
 // pyramids (k_lk_pyr per level and image), track every keypoint (k_lk_track), download.
-static int lk_track_impl(lh_handle* h, const lh_lk_input* in, lh_lk_result* out) {
-    if (!h || !in || !out) return LH_E_BADARG;
+// lk_enqueue: everything up to and including the tracking launch, on the handle's stream; *e0 is recorded in
+// front of the first kernel.  kp2 (host): the initial guess when in->has_initial.
+static int lk_enqueue(lh_handle* h, const lh_lk_input* in, const float* kp2, const uint8_t* success, hipEvent_t* e0_out) {
     if (in->levels != 1 && in->levels != LH_LK_MAX_LEVELS) return LH_E_BADARG;
     if (in->cols < 1 || in->rows < 1 || in->step < in->cols || in->n_points < 0) return LH_E_BADARG;
     if (!in->img1 || !in->img2) return LH_E_BADARG;
     const int n = in->n_points;
-    if (n > 0 && (!in->kp1 || !out->kp2 || !out->success)) return LH_E_BADARG;
+    if (n > 0 && (!in->kp1 || !kp2 || !success)) return LH_E_BADARG;
     if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
     // level sizes: cv::Size(cols * 0.5, rows * 0.5) truncated (algorithm.cpp:146-153)
     int cols[LH_LK_MAX_LEVELS], rows[LH_LK_MAX_LEVELS];
@@ -1711,7 +1717,7 @@ static int lk_track_impl(lh_handle* h, const lh_lk_input* in, lh_lk_result* out)
     if (n > 0) {
         HIPCHK(hipMemcpyAsync(h->k_kp1.p, in->kp1, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
         // without an initial guess kp2 is scaled but never read (dx = dy = 0 at the top level)
-        if (in->has_initial) HIPCHK(hipMemcpyAsync(h->k_kp2.p, out->kp2, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
+        if (in->has_initial) HIPCHK(hipMemcpyAsync(h->k_kp2.p, kp2, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
         else HIPCHK(hipMemsetAsync(h->k_kp2.p, 0, 2 * sizeof(float) * (size_t)n, s));
     }
     lh_lk_levels L[2];
@@ -1723,8 +1729,8 @@ static int lk_track_impl(lh_handle* h, const lh_lk_input* in, lh_lk_result* out)
             L[im].rows[l] = rows[ll];
             L[im].step[l] = step[ll];
         }
-    hipEvent_t e0 = next_event(h), e1 = next_event(h);
-    if (!e0 || !e1) return LH_E_HIP;
+    hipEvent_t e0 = next_event(h);
+    if (!e0) return LH_E_HIP;
     HIPCHK(hipEventRecord(e0, s));
     for (int l = 1; l < in->levels; ++l)
         for (int im = 0; im < 2; ++im)
@@ -1732,6 +1738,18 @@ static int lk_track_impl(lh_handle* h, const lh_lk_input* in, lh_lk_result* out)
                                     h->k_img[im].p + off[l], cols[l], rows[l]));
     HIPCHK(lh_launch_lk_track(s, &L[0], &L[1], in->levels, n, h->k_kp1.p, h->k_kp2.p, h->k_kp2.p, h->k_succ.p,
                               in->inverse ? 1 : 0, in->has_initial ? 1 : 0));
+    *e0_out = e0;
+    return LH_OK;
+}
+
+static int lk_track_impl(lh_handle* h, const lh_lk_input* in, lh_lk_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    hipEvent_t e0 = nullptr;
+    if (int st = lk_enqueue(h, in, out->kp2, out->success, &e0)) return st;
+    const int n = in->n_points;
+    hipStream_t s = h->stream;
+    hipEvent_t e1 = next_event(h);
+    if (!e1) return LH_E_HIP;
     HIPCHK(hipEventRecord(e1, s));
     if (n > 0) {
         HIPCHK(hipMemcpyAsync(out->kp2, h->k_kp2.p, 2 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -1741,6 +1759,143 @@ static int lk_track_impl(lh_handle* h, const lh_lk_input* in, lh_lk_result* out)
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     out->time_ms = ms;
+    h->event_next = 0;
+    return LH_OK;
+}
+
+// legoslam::triangulation (algorithm.h:11-34) for a batch of points (k_triangulate, lh_tri.hip).
+// The fields lh_triangulate and lh_stereo_landmarks share: threshold, gate, T_out, and the output arena
+// (pt [n][3], sing_ratio [n], flags [n]).
+struct TriOut { size_t o_ratio, o_flag, o_end; };
+static int tri_outputs(lh_handle* h, lh_tri_args* a, int n, double thr, int gate, double y_max, double z_min,
+                       double z_max, const double* T_out, TriOut* o) {
+    o->o_ratio = sizeof(double) * 3 * (size_t)n;
+    o->o_flag = o->o_ratio + sizeof(double) * (size_t)n;
+    o->o_end = o->o_flag + (size_t)n;
+    HIPCHK(h->t_out.ensure(o->o_end));
+    a->thr = thr;
+    a->gate = gate ? 1 : 0;
+    a->y_max = y_max; a->z_min = z_min; a->z_max = z_max;
+    a->has_T = T_out ? 1 : 0;
+    for (int i = 0; i < 12; ++i) a->T[i] = T_out ? T_out[i] : 0.0;
+    a->pt = (double*)h->t_out.p;
+    a->ratio = (double*)(h->t_out.p + o->o_ratio);
+    a->flags = h->t_out.p + o->o_flag;
+    return LH_OK;
+}
+
+static int32_t tri_count_accepted(const uint8_t* flags, int n) {
+    int32_t c = 0;
+    for (int i = 0; i < n; ++i) c += flags[i] == 0;
+    return c;
+}
+
+static int triangulate_impl(lh_handle* h, const lh_tri_input* in, lh_tri_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    const int n = in->n_points, P = in->n_poses;
+    if (n < 0) return LH_E_BADARG;
+    out->n_accepted = 0;
+    out->time_ms = 0.0;
+    if (n == 0) return LH_OK;
+    if (P < 1 || !in->pose_Tcw || !in->view_xy || !out->pt || !out->flags) return LH_E_BADARG;
+    if (in->view_ptr && !in->view_pose) return LH_E_BADARG;
+    int64_t nv;
+    if (in->view_ptr) {
+        if (in->view_ptr[0] < 0) return LH_E_BADARG;
+        for (int i = 0; i < n; ++i)
+            if (in->view_ptr[i + 1] - in->view_ptr[i] < 2) return LH_E_BADARG;   // fewer than 2 views, or decreasing
+        nv = in->view_ptr[n];
+        for (int64_t v = in->view_ptr[0]; v < nv; ++v)
+            if (in->view_pose[v] >= (uint32_t)P) return LH_E_BADARG;
+    } else {
+        if (P < 2) return LH_E_BADARG;
+        nv = (int64_t)n * P;
+    }
+    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
+    hipStream_t s = h->stream;
+    // input arena: doubles first, then the int64 CSR, then the 32-bit pose indices
+    const size_t i_K = sizeof(double) * 12 * (size_t)P;
+    const size_t i_xy = i_K + sizeof(double) * 4 * (size_t)P;
+    const size_t i_ptr = i_xy + sizeof(double) * 2 * (size_t)nv;
+    const size_t i_vp = i_ptr + (in->view_ptr ? sizeof(int64_t) * ((size_t)n + 1) : 0);
+    const size_t i_end = i_vp + (in->view_ptr ? sizeof(uint32_t) * (size_t)nv : 0);
+    HIPCHK(h->t_in.ensure(i_end));
+    uint8_t* ti = h->t_in.p;
+    lh_tri_args a{};
+    TriOut o;
+    if (int st = tri_outputs(h, &a, n, in->sing_ratio_thr, in->gate, in->y_max, in->z_min, in->z_max, in->T_out, &o))
+        return st;
+    HIPCHK(hipMemcpyAsync(ti, in->pose_Tcw, i_K, hipMemcpyHostToDevice, s));
+    if (in->cam_K) HIPCHK(hipMemcpyAsync(ti + i_K, in->cam_K, i_xy - i_K, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ti + i_xy, in->view_xy, i_ptr - i_xy, hipMemcpyHostToDevice, s));
+    if (in->view_ptr) {
+        HIPCHK(hipMemcpyAsync(ti + i_ptr, in->view_ptr, i_vp - i_ptr, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ti + i_vp, in->view_pose, i_end - i_vp, hipMemcpyHostToDevice, s));
+    }
+    a.n_points = n;
+    a.n_poses = P;
+    a.pose = (const double*)ti;
+    a.cam_K = in->cam_K ? (const double*)(ti + i_K) : nullptr;
+    a.view_xy = (const double*)(ti + i_xy);
+    a.view_ptr = in->view_ptr ? (const int64_t*)(ti + i_ptr) : nullptr;
+    a.view_pose = in->view_ptr ? (const uint32_t*)(ti + i_vp) : nullptr;
+    hipEvent_t e0 = next_event(h), e1 = next_event(h);
+    if (!e0 || !e1) return LH_E_HIP;
+    HIPCHK(hipEventRecord(e0, s));
+    HIPCHK(lh_launch_triangulate(s, &a));
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipMemcpyAsync(out->pt, a.pt, o.o_ratio, hipMemcpyDeviceToHost, s));
+    if (out->sing_ratio) HIPCHK(hipMemcpyAsync(out->sing_ratio, a.ratio, o.o_flag - o.o_ratio, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out->flags, a.flags, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    out->time_ms = ms;
+    out->n_accepted = tri_count_accepted(out->flags, n);
+    h->event_next = 0;
+    return LH_OK;
+}
+
+// lh_lk_track left -> right, then k_triangulate on kp1 / kp2 / success where the tracker left them
+static int stereo_landmarks_impl(lh_handle* h, const lh_stereo_input* in, lh_stereo_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    const int n = in->lk.n_points;
+    if (!in->pose_Tcw || (n > 0 && (!out->pt || !out->flags))) return LH_E_BADARG;
+    out->n_accepted = 0;
+    hipEvent_t e0 = nullptr;
+    if (int st = lk_enqueue(h, &in->lk, out->kp2, out->success, &e0)) return st;
+    hipStream_t s = h->stream;
+    const size_t i_K = sizeof(double) * 12 * 2, i_end = i_K + sizeof(double) * 4 * 2;
+    HIPCHK(h->t_in.ensure(i_end));
+    uint8_t* ti = h->t_in.p;
+    lh_tri_args a{};
+    TriOut o;
+    if (int st = tri_outputs(h, &a, n, in->sing_ratio_thr, in->gate, in->y_max, in->z_min, in->z_max, in->T_out, &o))
+        return st;
+    HIPCHK(hipMemcpyAsync(ti, in->pose_Tcw, i_K, hipMemcpyHostToDevice, s));
+    if (in->cam_K) HIPCHK(hipMemcpyAsync(ti + i_K, in->cam_K, i_end - i_K, hipMemcpyHostToDevice, s));
+    a.n_points = n;
+    a.n_poses = 2;
+    a.pose = (const double*)ti;
+    a.cam_K = in->cam_K ? (const double*)(ti + i_K) : nullptr;
+    a.kp1 = h->k_kp1.p;
+    a.kp2 = h->k_kp2.p;
+    a.success = h->k_succ.p;
+    HIPCHK(lh_launch_triangulate(s, &a));
+    hipEvent_t e1 = next_event(h);
+    if (!e1) return LH_E_HIP;
+    HIPCHK(hipEventRecord(e1, s));
+    if (n > 0) {
+        HIPCHK(hipMemcpyAsync(out->kp2, h->k_kp2.p, 2 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->success, h->k_succ.p, (size_t)n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->pt, a.pt, o.o_ratio, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->flags, a.flags, (size_t)n, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    out->time_ms = ms;
+    out->n_accepted = tri_count_accepted(out->flags, n);
     h->event_next = 0;
     return LH_OK;
 }
@@ -1757,6 +1912,22 @@ int lh_estimate_pose(lh_handle* h, const lh_frames* in, lh_frames_result* out) {
 int lh_lk_track(lh_handle* h, const lh_lk_input* in, lh_lk_result* out) {
     try {
         return lk_track_impl(h, in, out);
+    } catch (...) {
+        return LH_E_HIP;
+    }
+}
+
+int lh_triangulate(lh_handle* h, const lh_tri_input* in, lh_tri_result* out) {
+    try {
+        return triangulate_impl(h, in, out);
+    } catch (...) {
+        return LH_E_HIP;
+    }
+}
+
+int lh_stereo_landmarks(lh_handle* h, const lh_stereo_input* in, lh_stereo_result* out) {
+    try {
+        return stereo_landmarks_impl(h, in, out);
     } catch (...) {
         return LH_E_HIP;
     }

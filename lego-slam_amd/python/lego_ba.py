@@ -196,6 +196,35 @@ class LhLkResult(C.Structure):
     _fields_ = [("kp2", C.c_void_p), ("success", C.c_void_p), ("time_ms", C.c_double)]
 
 
+class LhTriInput(C.Structure):
+    _fields_ = [
+        ("n_points", C.c_int32), ("n_poses", C.c_int32), ("pose_Tcw", C.c_void_p), ("cam_K", C.c_void_p),
+        ("view_ptr", C.c_void_p), ("view_pose", C.c_void_p), ("view_xy", C.c_void_p), ("sing_ratio_thr", C.c_double),
+        ("gate", C.c_int32), ("y_max", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double), ("T_out", C.c_void_p),
+    ]
+
+
+class LhTriResult(C.Structure):
+    _fields_ = [("pt", C.c_void_p), ("flags", C.c_void_p), ("sing_ratio", C.c_void_p), ("n_accepted", C.c_int32),
+                ("time_ms", C.c_double)]
+
+
+class LhStereoInput(C.Structure):
+    _fields_ = [
+        ("lk", LhLkInput), ("pose_Tcw", C.c_void_p), ("cam_K", C.c_void_p), ("sing_ratio_thr", C.c_double),
+        ("gate", C.c_int32), ("y_max", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double), ("T_out", C.c_void_p),
+    ]
+
+
+class LhStereoResult(C.Structure):
+    _fields_ = [("kp2", C.c_void_p), ("success", C.c_void_p), ("pt", C.c_void_p), ("flags", C.c_void_p),
+                ("n_accepted", C.c_int32), ("time_ms", C.c_double)]
+
+
+# lh_tri_result.flags
+LH_TRI_NONFINITE, LH_TRI_RATIO, LH_TRI_Y, LH_TRI_Z, LH_TRI_TRACK = 1, 2, 4, 8, 16
+
+
 class LhKernelStats(C.Structure):
     _fields_ = [("launches", C.c_int64 * 8), ("total_ms", C.c_double * 8)]
 
@@ -205,7 +234,7 @@ ABI_SYMBOLS = [
     "lh_strerror", "lh_default_options", "lh_default_options_v", "lh_kernel_name", "lh_comm_unique_id",
     "lh_create", "lh_destroy", "lh_solve", "lh_upload", "lh_solve_resident",
     "lh_kernel_stats_get", "lh_kernel_stats_reset", "lh_classify_outliers", "lh_set_profiling",
-    "lh_estimate_pose", "lh_lk_track",
+    "lh_estimate_pose", "lh_lk_track", "lh_triangulate", "lh_stereo_landmarks",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
     "lh_debug_batch",
@@ -238,6 +267,9 @@ def ba_lib():
         lib.lh_set_profiling.argtypes = [C.c_void_p, C.c_int]
         lib.lh_estimate_pose.argtypes = [C.c_void_p, C.POINTER(LhFrames), C.POINTER(LhFramesResult)]
         lib.lh_lk_track.argtypes = [C.c_void_p, C.POINTER(LhLkInput), C.POINTER(LhLkResult)]
+        if hasattr(lib, "lh_triangulate"):   # (an older library of an A/B run lacks them)
+            lib.lh_triangulate.argtypes = [C.c_void_p, C.POINTER(LhTriInput), C.POINTER(LhTriResult)]
+            lib.lh_stereo_landmarks.argtypes = [C.c_void_p, C.POINTER(LhStereoInput), C.POINTER(LhStereoResult)]
         lib.lh_classify_outliers.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lh_debug_event_floor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -424,10 +456,9 @@ class Solver:
         _check(ba_lib().lh_solve_resident(self.h, C.byref(r)), "lh_solve_resident")
         return self._finish(r, out)
 
-    def lk_track(self, img1, img2, kp1, kp2_init=None, inverse=False, levels=4):
-        """LKOpticalFlow4Layer (levels=4) / LKOpticalFlow1Layer (levels=1) of algorithm.cpp on 8-bit
-        images (2-D uint8 arrays, rows contiguous).  Returns kp2 [n, 2] float32, success [n] bool and
-        the device time."""
+    @staticmethod
+    def _lk_input(img1, img2, kp1, kp2_init, inverse, levels):
+        """An LhLkInput on 8-bit images, the arrays it points to, and the kp2 / success buffers."""
         i1 = np.ascontiguousarray(img1, dtype=np.uint8)
         i2 = np.ascontiguousarray(img2, dtype=np.uint8)
         if i1.shape != i2.shape or i1.ndim != 2:
@@ -443,10 +474,82 @@ class Solver:
         a.img1, a.img2 = _ptr(i1), _ptr(i2)
         a.n_points, a.kp1 = n, _ptr(k1)
         a.inverse, a.has_initial, a.levels = int(bool(inverse)), int(kp2_init is not None), int(levels)
+        return a, (i1, i2, k1), k2, ok
+
+    def lk_track(self, img1, img2, kp1, kp2_init=None, inverse=False, levels=4):
+        """LKOpticalFlow4Layer (levels=4) / LKOpticalFlow1Layer (levels=1) of algorithm.cpp on 8-bit
+        images (2-D uint8 arrays, rows contiguous).  Returns kp2 [n, 2] float32, success [n] bool and
+        the device time."""
+        a, _keep, k2, ok = self._lk_input(img1, img2, kp1, kp2_init, inverse, levels)
         r = LhLkResult()
         r.kp2, r.success = _ptr(k2), _ptr(ok)
         _check(ba_lib().lh_lk_track(self.h, C.byref(a), C.byref(r)), "lh_lk_track")
         return dict(kp2=k2, success=ok.astype(bool), time_ms=r.time_ms)
+
+    @staticmethod
+    def _tri_common(s, keep, thr, gate, T_out):
+        """The threshold, gate (y_max, z_min, z_max) and T_out fields LhTriInput and LhStereoInput share."""
+        s.sing_ratio_thr = float(thr)
+        if gate is not None:
+            s.gate = 1
+            s.y_max, s.z_min, s.z_max = (float(g) for g in gate)
+        keep["T"] = None if T_out is None else np.ascontiguousarray(T_out, np.float64).reshape(12)
+        s.T_out = _ptr(keep["T"])
+
+    def triangulate(self, poses, view_xy, view_ptr=None, view_pose=None, K=None, thr=1e-3, gate=None, T_out=None):
+        """legoslam::triangulation (algorithm.h:11-34) on a batch of points through lh_triangulate.
+        poses [P, 12] (or [P, 3, 4]) row-major [R|t]; view_xy [n_views, 2] normalised coordinates, or pixels
+        with K [P, 4] (fx, fy, cx, cy per pose).  Without view_ptr every point has P views in pose order
+        (view_xy [n, P, 2]); with it, view_ptr [n + 1] and view_pose [n_views] are a CSR over the views.
+        gate: (y_max, z_min, z_max) or None; T_out: [12] applied to accepted points.
+        Returns dict(pt [n, 3], flags [n] uint8, sing_ratio [n], n_accepted, time_ms)."""
+        keep = dict(pose=np.ascontiguousarray(poses, np.float64).reshape(-1, 12),
+                    xy=np.ascontiguousarray(view_xy, np.float64).reshape(-1, 2),
+                    ptr=_as(view_ptr, np.int64), vp=_as(view_pose, np.uint32),
+                    K=None if K is None else np.ascontiguousarray(K, np.float64).reshape(-1, 4))
+        P = keep["pose"].shape[0]
+        if keep["K"] is not None and keep["K"].shape[0] != P:
+            raise ValueError("K must hold one (fx, fy, cx, cy) per pose")
+        if keep["ptr"] is None:
+            if P == 0 or keep["xy"].shape[0] % P:
+                raise ValueError("view_xy must hold n_poses views per point")
+            n = keep["xy"].shape[0] // P
+        else:
+            n = keep["ptr"].shape[0] - 1
+            if keep["vp"] is None or n < 0 or (n > 0 and (keep["vp"].shape[0] < keep["ptr"][-1]
+                                                          or keep["xy"].shape[0] < keep["ptr"][-1])):
+                raise ValueError("view_pose and view_xy must cover view_ptr")
+        s = LhTriInput()
+        s.n_points, s.n_poses = n, P
+        s.pose_Tcw, s.cam_K, s.view_xy = _ptr(keep["pose"]), _ptr(keep["K"]), _ptr(keep["xy"])
+        s.view_ptr, s.view_pose = _ptr(keep["ptr"]), _ptr(keep["vp"])
+        self._tri_common(s, keep, thr, gate, T_out)
+        out = dict(pt=np.zeros((n, 3)), flags=np.zeros(n, np.uint8), sing_ratio=np.zeros(n))
+        r = LhTriResult()
+        r.pt, r.flags, r.sing_ratio = _ptr(out["pt"]), _ptr(out["flags"]), _ptr(out["sing_ratio"])
+        _check(ba_lib().lh_triangulate(self.h, C.byref(s), C.byref(r)), "lh_triangulate")
+        out["n_accepted"], out["time_ms"] = r.n_accepted, r.time_ms
+        return out
+
+    def stereo_landmarks(self, img_left, img_right, kp_left, poses, K=None, kp_right_init=None, levels=4, thr=1e-3,
+                         gate=None, T_out=None):
+        """One stereo frame through lh_stereo_landmarks: lk_track left -> right, then triangulate on the tracked
+        pairs without leaving the device.  poses [2, 12] and K [2, 4]: the left and right cameras.
+        Returns dict(kp2, success, pt, flags, n_accepted, time_ms); a failed track carries flag bit 4."""
+        s = LhStereoInput()
+        s.lk, _keep_lk, k2, ok = self._lk_input(img_left, img_right, kp_left, kp_right_init, False, levels)
+        n = s.lk.n_points
+        keep = dict(pose=np.ascontiguousarray(poses, np.float64).reshape(2, 12),
+                    K=None if K is None else np.ascontiguousarray(K, np.float64).reshape(2, 4))
+        s.pose_Tcw, s.cam_K = _ptr(keep["pose"]), _ptr(keep["K"])
+        self._tri_common(s, keep, thr, gate, T_out)
+        out = dict(kp2=k2, pt=np.zeros((n, 3)), flags=np.zeros(n, np.uint8))
+        r = LhStereoResult()
+        r.kp2, r.success, r.pt, r.flags = _ptr(k2), _ptr(ok), _ptr(out["pt"]), _ptr(out["flags"])
+        _check(ba_lib().lh_stereo_landmarks(self.h, C.byref(s), C.byref(r)), "lh_stereo_landmarks")
+        out["success"] = ok.astype(bool)
+        out["n_accepted"], out["time_ms"] = r.n_accepted, r.time_ms
+        return out
 
     def estimate_pose(self, fb, is_outlier_in=None):
         """Frontend::EstimateCurrentPose on every frame of batch `fb` (obs_ptr CSR, pose_Tcw, pts,
