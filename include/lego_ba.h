@@ -377,6 +377,56 @@ typedef struct lh_stereo_result {
 } lh_stereo_result;
 int lh_stereo_landmarks(lh_handle *h, const lh_stereo_input *in, lh_stereo_result *out);
 
+/*
+ * Shi-Tomasi corner detection, replacing Frontend::DetectFeatures (src/frontend_lego.cpp:292-310): a mask with a
+ * box of +-10 pixels cleared around every feature the frame already has (:294-297), then
+ *   gftt_ = cv::GFTTDetector::create(num_features, 0.01, 20);  gftt_->detect(left_img, keypoints, mask)  (:16, :300)
+ * i.e. cv::goodFeaturesToTrack with blockSize 3, the Sobel aperture 3 and no Harris detector.  The quantities are
+ * OpenCV's, defined in exact arithmetic (OpenCV's own float32 path is not specified to the bit):
+ *   gx, gy     integer Sobel 3x3 gradients of the 8-bit image, BORDER_REFLECT_101
+ *   A, B, C    the sums of gx gx, gx gy, gy gy over the 3x3 block, the product images extended by REFLECT_101
+ *   lambda     (double)(A + C) - sqrt((double)((A - C)^2 + 4 B^2)): 2 * 3060^2 times cornerMinEigenVal's value
+ *   allowed    the mask byte is nonzero and the pixel lies in no box [rint(p - half), rint(p + half)] of an
+ *              exclusion point p (float32 arithmetic, round half to even, both ends inclusive, clipped to the image)
+ *   lambda_max the largest lambda over allowed pixels, border pixels included; none, or lambda_max <= 0: no corners
+ *   candidates allowed pixels with 1 <= x <= cols - 2, 1 <= y <= rows - 2, lambda > quality_level * lambda_max and
+ *              lambda >= each of the 8 neighbours' (whatever their mask; equal neighbours both stay)
+ *   selection  in descending lambda, ties to the larger y * cols + x first (OpenCV 4): a candidate is accepted unless
+ *              an accepted one lies at a squared distance < min_distance^2; min_distance < 1: all are accepted
+ * kp holds the first max_corners accepted points in that order as (x, y), usable as lh_lk_input.kp1
+ * (cv::KeyPoint::size, 3, is not returned).  With max_corners <= 0 there is no limit: at most kp_capacity corners
+ * are written and n_corners is the true count.
+ *
+ * LH_E_BADARG: a null required pointer, cols < 3 or rows < 3, rows * cols > INT32_MAX, step < cols (mask_step
+ * likewise), a negative count, kp_capacity < max_corners when max_corners > 0, a negative or NaN quality_level or
+ * min_distance.
+ */
+typedef struct lh_detect_input {
+    int32_t cols, rows;
+    int64_t step;               /* bytes per image row (>= cols) */
+    const uint8_t *img;         /* [rows][step] 8-bit gray */
+    const uint8_t *mask;        /* [rows][mask_step] nonzero: allowed; NULL: all allowed */
+    int64_t mask_step;
+    int32_t n_exclude;
+    const float *exclude_pt;    /* [n_exclude][2] position_.pt of the frame's existing features */
+    float exclude_half;         /* 10 (frontend_lego.cpp:295-296) */
+    int32_t max_corners;        /* num_features = 150; <= 0: no limit */
+    double quality_level;       /* 0.01 */
+    double min_distance;        /* 20 */
+} lh_detect_input;
+typedef struct lh_detect_result {
+    float *kp;                  /* [kp_capacity][2] */
+    int32_t kp_capacity;
+    double *response;           /* [kp_capacity] lambda of each corner, or NULL */
+    double *eig;                /* [rows][cols] the whole lambda image, or NULL (tests) */
+    int32_t n_corners;
+    int32_t n_candidates;
+    double lambda_max;          /* 0 when no pixel is allowed */
+    double time_ms;             /* device time, first kernel to last (the host's checks between selection rounds
+                                   included; copies of the inputs and outputs excluded) */
+} lh_detect_result;
+int lh_detect_features(lh_handle *h, const lh_detect_input *in, lh_detect_result *out);
+
 /* ---- test hooks (not part of the reference interface) ---- */
 /* f64 MFMA accumulator-layout probe: D(16x16) = A(16x4) * B(4x16), device pointers, row-major */
 int lh_debug_mfma_probe(const double *A, const double *B, double *D);

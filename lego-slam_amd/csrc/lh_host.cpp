@@ -23,6 +23,7 @@
 
 #include "../../include/lego_ba.h"
 #include "lh_common.h"
+#include "lh_gftt.h"
 #include "lh_lk.h"
 #include "lh_plan.h"
 #include "lh_tri.h"
@@ -73,6 +74,9 @@ hipError_t lh_launch_frames(hipStream_t st, int n_frames, const int64_t* obs_ptr
                             double* pose_out, uint8_t* flag_out, double* rchi2_out, int32_t* iters_out,
                             int32_t* inliers_out);
 hipError_t lh_launch_triangulate(hipStream_t st, const lh_tri_args* a);
+hipError_t lh_launch_gftt_front(hipStream_t st, const lh_gftt_args* a);
+hipError_t lh_launch_gftt_rounds(hipStream_t st, const lh_gftt_args* a, int first, int count);
+hipError_t lh_launch_gftt_order(hipStream_t st, const lh_gftt_args* a);
 }
 
 namespace {
@@ -334,6 +338,13 @@ struct lh_handle {
     DevBuf<float> k_kp1, k_kp2;
     // triangulation (lh_triangulate, lh_stereo_landmarks): the inputs packed into one arena, the outputs into another
     DevBuf<uint8_t> t_in, t_out;
+    // feature detection (lh_detect_features): image, allow and state bytes; lambda; candidate and corner lists
+    DevBuf<uint8_t> g_img, g_allow, g_state;
+    DevBuf<double> g_eig, g_acc_lam, g_resp;
+    DevBuf<uint32_t> g_cand, g_acc_idx;
+    DevBuf<float> g_excl, g_kp;
+    DevBuf<lh_gftt_ctl> g_ctl;
+    HostBuf<lh_gftt_ctl> s_gctl;   // pinned: read back once per batch of selection rounds
     lh_ctrl* h_ctrl = nullptr;   // pinned
     int last_chains = -1;        // lh_debug_chains: the last synchronous solve's stop chain
     int last_lskips = -1;        // lh_debug_ladder: its rejections onto a built ladder rung
@@ -1515,6 +1526,9 @@ void lh_destroy(lh_handle* h) {
     h->f_in.release(); h->f_out.release(); h->f_res.release(); h->s_fin.release(); h->s_fout.release();
     h->k_img[0].release(); h->k_img[1].release(); h->k_succ.release(); h->k_kp1.release(); h->k_kp2.release();
     h->t_in.release(); h->t_out.release();
+    h->g_img.release(); h->g_allow.release(); h->g_state.release(); h->g_eig.release(); h->g_acc_lam.release();
+    h->g_resp.release(); h->g_cand.release(); h->g_acc_idx.release(); h->g_excl.release(); h->g_kp.release();
+    h->g_ctl.release(); h->s_gctl.release();
     h->d_chunks.release(); h->d_sbs.release(); h->d_meta.release(); h->d_obs_perm.release(); h->d_lm_perm.release();
     h->d_pair_ptr.release(); h->d_items.release(); h->d_pair_pq.release(); h->d_lm_in.release();
     h->d_uv.release(); h->d_rec.release(); h->d_ptab.release(); h->d_out_xyz.release(); h->d_out_rho.release();
@@ -1900,6 +1914,97 @@ static int stereo_landmarks_impl(lh_handle* h, const lh_stereo_input* in, lh_ste
     return LH_OK;
 }
 
+// Frontend::DetectFeatures (frontend_lego.cpp:292-310): the mask's exclusion boxes, then cv::GFTTDetector's
+// corners, defined in exact arithmetic (lh_gftt.h).  The image, lambda and every list stay on
+// the device; the host reads one lh_gftt_ctl per batch of selection rounds, to know when none is left open.
+#define LH_GFTT_ROUND_BATCH 8   // a round that finds nothing open costs a launch; a check costs a synchronise
+static int detect_features_impl(lh_handle* h, const lh_detect_input* in, lh_detect_result* out) {
+    if (!h || !in || !out || !in->img) return LH_E_BADARG;
+    const int cols = in->cols, rows = in->rows;
+    if (cols < 3 || rows < 3 || in->step < cols || (int64_t)rows * cols > INT32_MAX) return LH_E_BADARG;
+    if (in->mask && in->mask_step < cols) return LH_E_BADARG;
+    if (in->n_exclude < 0 || (in->n_exclude > 0 && !in->exclude_pt)) return LH_E_BADARG;
+    if (out->kp_capacity < 0 || (out->kp_capacity > 0 && !out->kp)) return LH_E_BADARG;
+    if (in->max_corners > 0 && out->kp_capacity < in->max_corners) return LH_E_BADARG;
+    if (!(in->quality_level >= 0.0) || !(in->min_distance >= 0.0)) return LH_E_BADARG;
+    out->n_corners = out->n_candidates = 0;
+    out->lambda_max = 0.0;
+    out->time_ms = 0.0;
+    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
+    hipStream_t s = h->stream;
+    const size_t px = (size_t)rows * (size_t)cols;
+    const int limit = in->max_corners > 0 ? in->max_corners : out->kp_capacity;
+    HIPCHK(h->g_img.ensure(px));
+    HIPCHK(h->g_allow.ensure(px));
+    HIPCHK(h->g_state.ensure(px + 4));   // k_gftt_round reads it by aligned words
+    HIPCHK(h->g_eig.ensure(px));
+    HIPCHK(h->g_cand.ensure(px));
+    HIPCHK(h->g_acc_idx.ensure(px));
+    HIPCHK(h->g_acc_lam.ensure(px));
+    HIPCHK(h->g_excl.ensure(2 * (size_t)std::max(in->n_exclude, 1)));
+    HIPCHK(h->g_kp.ensure(2 * (size_t)std::max(limit, 1)));
+    HIPCHK(h->g_resp.ensure((size_t)std::max(limit, 1)));
+    HIPCHK(h->g_ctl.ensure(1));
+    HIPCHK(h->s_gctl.ensure(1));
+    // rows packed to `cols` bytes: only `cols` bytes of a caller's row are readable (a cv::Mat ROI has step > cols)
+    auto upload_rows = [&](uint8_t* dst, const uint8_t* src, int64_t step) {
+        if (step == cols) return hipMemcpyAsync(dst, src, px, hipMemcpyHostToDevice, s);
+        return hipMemcpy2DAsync(dst, (size_t)cols, src, (size_t)step, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice, s);
+    };
+    HIPCHK(upload_rows(h->g_img.p, in->img, in->step));
+    if (in->mask)
+        HIPCHK(upload_rows(h->g_allow.p, in->mask, in->mask_step));
+    else
+        HIPCHK(hipMemsetAsync(h->g_allow.p, 1, px, s));
+    if (in->n_exclude > 0)
+        HIPCHK(hipMemcpyAsync(h->g_excl.p, in->exclude_pt, 2 * sizeof(float) * (size_t)in->n_exclude, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->g_ctl.p, 0, sizeof(lh_gftt_ctl), s));
+    lh_gftt_args a{};
+    a.cols = cols; a.rows = rows;
+    a.img = h->g_img.p; a.allow = h->g_allow.p;
+    a.n_exclude = in->n_exclude; a.exclude_pt = h->g_excl.p; a.exclude_half = in->exclude_half;
+    a.quality = in->quality_level;
+    a.min_dist2 = in->min_distance * in->min_distance;
+    // candidates nearer than min_distance differ by at most ceil(min_distance) - 1 pixels along an axis
+    a.reach = in->min_distance < 1.0 ? -1 : (int)std::min(std::ceil(in->min_distance) - 1.0, (double)std::max(cols, rows));
+    a.limit = limit;
+    a.eig = h->g_eig.p; a.state = h->g_state.p; a.cand = h->g_cand.p;
+    a.acc_idx = h->g_acc_idx.p; a.acc_lam = h->g_acc_lam.p;
+    a.kp = h->g_kp.p; a.response = h->g_resp.p; a.ctl = h->g_ctl.p;
+    hipEvent_t e0 = next_event(h), e1 = next_event(h);
+    if (!e0 || !e1) return LH_E_HIP;
+    HIPCHK(hipEventRecord(e0, s));
+    HIPCHK(lh_launch_gftt_front(s, &a));
+    const lh_gftt_ctl& ctl = *h->s_gctl.p;
+    if (a.reach >= 0)
+        for (int r = 0;; r += LH_GFTT_ROUND_BATCH) {   // a round decides at least the strongest open candidate
+            HIPCHK(lh_launch_gftt_rounds(s, &a, r, LH_GFTT_ROUND_BATCH));
+            HIPCHK(hipMemcpyAsync(h->s_gctl.p, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (ctl.open[(r + LH_GFTT_ROUND_BATCH - 1) % 3] == 0) break;
+        }
+    HIPCHK(lh_launch_gftt_order(s, &a));
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipMemcpyAsync(h->s_gctl.p, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    if (out->eig) HIPCHK(hipMemcpyAsync(out->eig, a.eig, sizeof(double) * px, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t n_written = std::min<int64_t>(ctl.n_acc, limit);
+    if (n_written > 0) {
+        HIPCHK(hipMemcpyAsync(out->kp, a.kp, 2 * sizeof(float) * (size_t)n_written, hipMemcpyDeviceToHost, s));
+        if (out->response)
+            HIPCHK(hipMemcpyAsync(out->response, a.response, sizeof(double) * (size_t)n_written, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    out->time_ms = ms;
+    out->n_corners = in->max_corners > 0 ? (int32_t)n_written : (int32_t)ctl.n_acc;
+    out->n_candidates = (int32_t)ctl.n_cand;
+    out->lambda_max = ctl.max_key ? lh_gftt_unkey(ctl.max_key) : 0.0;
+    h->event_next = 0;
+    return LH_OK;
+}
+
 // the staging copies build std::vectors (par_copy): no exception crosses the ABI
 int lh_estimate_pose(lh_handle* h, const lh_frames* in, lh_frames_result* out) {
     try {
@@ -1928,6 +2033,14 @@ int lh_triangulate(lh_handle* h, const lh_tri_input* in, lh_tri_result* out) {
 int lh_stereo_landmarks(lh_handle* h, const lh_stereo_input* in, lh_stereo_result* out) {
     try {
         return stereo_landmarks_impl(h, in, out);
+    } catch (...) {
+        return LH_E_HIP;
+    }
+}
+
+int lh_detect_features(lh_handle* h, const lh_detect_input* in, lh_detect_result* out) {
+    try {
+        return detect_features_impl(h, in, out);
     } catch (...) {
         return LH_E_HIP;
     }

@@ -221,6 +221,20 @@ class LhStereoResult(C.Structure):
                 ("n_accepted", C.c_int32), ("time_ms", C.c_double)]
 
 
+class LhDetectInput(C.Structure):
+    _fields_ = [
+        ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int64), ("img", C.c_void_p), ("mask", C.c_void_p),
+        ("mask_step", C.c_int64), ("n_exclude", C.c_int32), ("exclude_pt", C.c_void_p), ("exclude_half", C.c_float),
+        ("max_corners", C.c_int32), ("quality_level", C.c_double), ("min_distance", C.c_double),
+    ]
+
+
+class LhDetectResult(C.Structure):
+    _fields_ = [("kp", C.c_void_p), ("kp_capacity", C.c_int32), ("response", C.c_void_p), ("eig", C.c_void_p),
+                ("n_corners", C.c_int32), ("n_candidates", C.c_int32), ("lambda_max", C.c_double),
+                ("time_ms", C.c_double)]
+
+
 # lh_tri_result.flags
 LH_TRI_NONFINITE, LH_TRI_RATIO, LH_TRI_Y, LH_TRI_Z, LH_TRI_TRACK = 1, 2, 4, 8, 16
 
@@ -234,7 +248,7 @@ ABI_SYMBOLS = [
     "lh_strerror", "lh_default_options", "lh_default_options_v", "lh_kernel_name", "lh_comm_unique_id",
     "lh_create", "lh_destroy", "lh_solve", "lh_upload", "lh_solve_resident",
     "lh_kernel_stats_get", "lh_kernel_stats_reset", "lh_classify_outliers", "lh_set_profiling",
-    "lh_estimate_pose", "lh_lk_track", "lh_triangulate", "lh_stereo_landmarks",
+    "lh_estimate_pose", "lh_lk_track", "lh_triangulate", "lh_stereo_landmarks", "lh_detect_features",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
     "lh_debug_batch",
@@ -270,6 +284,8 @@ def ba_lib():
         if hasattr(lib, "lh_triangulate"):   # (an older library of an A/B run lacks them)
             lib.lh_triangulate.argtypes = [C.c_void_p, C.POINTER(LhTriInput), C.POINTER(LhTriResult)]
             lib.lh_stereo_landmarks.argtypes = [C.c_void_p, C.POINTER(LhStereoInput), C.POINTER(LhStereoResult)]
+        if hasattr(lib, "lh_detect_features"):
+            lib.lh_detect_features.argtypes = [C.c_void_p, C.POINTER(LhDetectInput), C.POINTER(LhDetectResult)]
         lib.lh_classify_outliers.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lh_debug_event_floor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -549,6 +565,45 @@ class Solver:
         _check(ba_lib().lh_stereo_landmarks(self.h, C.byref(s), C.byref(r)), "lh_stereo_landmarks")
         out["success"] = ok.astype(bool)
         out["n_accepted"], out["time_ms"] = r.n_accepted, r.time_ms
+        return out
+
+    def detect_features(self, img, exclude=None, mask=None, max_corners=150, quality=0.01, min_distance=20.0,
+                        want_eig=False, exclude_half=10.0, capacity=None):
+        """Frontend::DetectFeatures (frontend_lego.cpp:292-310) through lh_detect_features: Shi-Tomasi corners of an
+        8-bit image (2-D uint8 array, rows contiguous), outside the +-exclude_half boxes around the points
+        `exclude` [m, 2] and where `mask` (same shape, optional) is nonzero.  max_corners <= 0: no limit; then
+        `capacity` corners are returned at most (default: one per pixel).
+        Returns dict(kp [n, 2] float32 (x, y), response [n], n_corners, n_candidates, lambda_max, time_ms) and,
+        with want_eig, eig [rows, cols]."""
+        im = np.asarray(img)
+        if im.ndim != 2 or im.dtype != np.uint8 or im.strides[1] != 1 or im.strides[0] < im.shape[1]:
+            im = np.ascontiguousarray(img, dtype=np.uint8)
+        if im.ndim != 2:
+            raise ValueError("the image must be a 2-D uint8 array")
+        rows, cols = im.shape
+        keep = dict(mask=None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8),
+                    ex=None if exclude is None else np.ascontiguousarray(exclude, dtype=np.float32).reshape(-1, 2))
+        if keep["mask"] is not None and keep["mask"].shape != im.shape:
+            raise ValueError("the mask must have the image's shape")
+        a = LhDetectInput()
+        a.cols, a.rows, a.step, a.img = cols, rows, im.strides[0], _ptr(im)
+        if keep["mask"] is not None:
+            a.mask, a.mask_step = _ptr(keep["mask"]), keep["mask"].strides[0]
+        a.n_exclude = 0 if keep["ex"] is None else keep["ex"].shape[0]
+        a.exclude_pt = _ptr(keep["ex"]) if a.n_exclude else None
+        a.exclude_half = float(exclude_half)
+        a.max_corners, a.quality_level, a.min_distance = int(max_corners), float(quality), float(min_distance)
+        cap = int(max_corners) if max_corners > 0 else (rows * cols if capacity is None else int(capacity))
+        kp, resp = np.zeros((cap, 2), np.float32), np.zeros(cap)
+        eig = np.zeros((rows, cols)) if want_eig else None
+        r = LhDetectResult()
+        r.kp, r.kp_capacity, r.response, r.eig = _ptr(kp), cap, _ptr(resp), _ptr(eig)
+        _check(ba_lib().lh_detect_features(self.h, C.byref(a), C.byref(r)), "lh_detect_features")
+        n = min(r.n_corners, cap)
+        out = dict(kp=kp[:n], response=resp[:n], n_corners=r.n_corners, n_candidates=r.n_candidates,
+                   lambda_max=r.lambda_max, time_ms=r.time_ms)
+        if want_eig:
+            out["eig"] = eig
         return out
 
     def estimate_pose(self, fb, is_outlier_in=None):
