@@ -19,7 +19,7 @@
 // No floating-point atomic touches a value that reaches the output.
 #include <hip/hip_runtime.h>
 
-#include "lh_gftt.h"
+#include "lh_launch.h"
 
 #define GF_TW 32
 #define GF_TH 8

@@ -1,150 +1,59 @@
-// lh_host.cpp — C ABI (include/lego_ba.h) of the MI355X BA solver: device buffers, the upload of
-// a window (lh_plan.cpp preprocessing into pinned staging, one async copy per array), the LM launch
-// loop, the per-trial exchange of a landmark-sharded solve, and the download of the results.
+// lh_host.cpp — C ABI (include/lego_ba.h) of the MI355X BA solver: the handle's life (lh_handle.h), the upload of
+// a window (lh_plan.cpp preprocessing into pinned staging, one async copy per array), the LM launch loop, the per-trial
+// exchange of a landmark-sharded solve, the download of the results.  (The frontend entry points: lh_frontend.cpp.)
 //
 // Per solve nothing but kernel launches happens on the host: the whole LM loop (accept/reject,
 // lambda schedule, stop rule) runs on the device, and the host keeps `depth` trials enqueued ahead
 // of the device's progress word.  With >1 rank each trial carries one all-reduce of the packed
 // reduced pose system; every rank issues exactly the same number of them (lh_plan.h, the trial schedule).
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 #include <sched.h>
 
-#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <new>
-#include <vector>
 
-#include "../../include/lego_ba.h"
-#include "lh_common.h"
-#include "lh_gftt.h"
-#include "lh_lk.h"
-#include "lh_plan.h"
-#include "lh_tri.h"
+#include "lh_handle.h"
+#include "lh_launch.h"
 
-extern "C" {
-hipError_t lh_prepare_lin(int lds_limit);
-size_t lh_lin_smem(int T, int ncam);
-hipError_t lh_launch_nop(hipStream_t st);
-hipError_t lh_launch_outliers(hipStream_t st, const double* rho, const int32_t* obs_perm, long nslots, long n_obs,
-                              double th0, unsigned* part, uint8_t* flags);
-hipError_t lh_launch_p2p(hipStream_t st, double* rs, double* maxd, int n, lh_peers peers, int rank, int world,
-                         int parity, unsigned long long tag, long slot, int mode, int* err);
-hipError_t lh_launch_outlier_counts(hipStream_t st, const double* rho, const int32_t* obs_perm, long nslots, long n_obs,
-                                    double th0, unsigned* part, double* tot);
-hipError_t lh_launch_outlier_flags(hipStream_t st, const double* rho, const int32_t* obs_perm, long nslots, long n_obs,
-                                   double th0, const double* gtot, uint8_t* flags);
-hipError_t lh_launch_lin(int T, int trial, int nchunks, int chunk_base, hipStream_t st, const lh_chunk* chunks,
-                         const lh_subbatch* sbs, const float* obs_uv, const uint32_t* obs_meta, double* rec,
-                         double* ptab, const double* ext, const lh_ctrl* ctrl, const double* dxp,
-                         double* edge_rho, double* rows, double* csc, const uint32_t* crow, uint8_t* wflag,
-                         long nslots, lh_params prm, int nrec, const uint64_t* fixed_bits, double* pose_mat,
-                         int writer, lh_reset_args rst);
-hipError_t lh_launch_reduce(hipStream_t st, const double* rows, const double* csc, const uint32_t* red_tab, int nred,
-                            lh_ctrl* ctrl, double* rs_stage, double* rs_commit, double* maxd,
-                            lh_params prm, int n_chunks, int mode, int* host_done, int seq, double* img);
-hipError_t lh_launch_img_init(hipStream_t st, double* img, int n);
-hipError_t lh_launch_ldlt_g_probe(const double* S, const double* b, int n, double* x, double* gA);
-hipError_t lh_launch_ctrl(hipStream_t st, lh_ctrl* ctrl, double* rs_commit, const double* rs_stage, const double* maxd,
-                          const uint32_t* rsmap, const uint16_t* pair_pq, double* dxp, lh_params prm, int mode,
-                          int* host_done, int seq, double* gA, const double* gS,
-                          const int32_t* brow_ptr, const uint32_t* brow_ent, const uint16_t* units, lh_band_args band,
-                          double* img, int kind);
-hipError_t lh_launch_dense(hipStream_t st, const double* rs_stage, const uint16_t* pair_pq, const lh_ctrl* ctrl,
-                           double* gS, int P);
-hipError_t lh_launch_gather(hipStream_t st, const lh_ctrl* ctrl, const double* rec, const int32_t* lm_perm, int nrec,
-                            const double* rho, const int32_t* obs_perm, long nslots, double* out_xyz, double* out_rho);
-hipError_t lh_launch_ldlt_probe(const double* S, const double* b, int n, double* x, int solver, double tol, int max_it,
-                                int* iters);
-hipError_t lh_launch_mfma_probe(const double* A, const double* B, double* D);
-hipError_t lh_read_stamps(unsigned long long* out, int n, int reset);
-hipError_t lh_launch_lk_pyr(hipStream_t st, const uint8_t* src, int sw, int sh, int64_t sstep, uint8_t* dst, int dw,
-                            int dh);
-hipError_t lh_launch_lk_track(hipStream_t st, const lh_lk_levels* L1, const lh_lk_levels* L2, int levels, int n,
-                              const float* kp1, const float* kp2_in, float* kp2_out, uint8_t* success, int inverse,
-                              int has_initial);
-hipError_t lh_launch_frames(hipStream_t st, int n_frames, const int64_t* obs_ptr, const double* pose_in,
-                            const double* pts, const double* uv, const uint8_t* flag_in, lh_params prm, double* res,
-                            double* pose_out, uint8_t* flag_out, double* rchi2_out, int32_t* iters_out,
-                            int32_t* inliers_out);
-hipError_t lh_launch_triangulate(hipStream_t st, const lh_tri_args* a);
-hipError_t lh_launch_gftt_front(hipStream_t st, const lh_gftt_args* a);
-hipError_t lh_launch_gftt_rounds(hipStream_t st, const lh_gftt_args* a, int first, int count);
-hipError_t lh_launch_gftt_order(hipStream_t st, const lh_gftt_args* a);
+using namespace lh;
+
+hipEvent_t lh::next_event(lh_handle* h) {
+    if (h->event_next == h->event_pool.size()) {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return nullptr;
+        h->event_pool.push_back(e);
+    }
+    return h->event_pool[h->event_next++];
+}
+
+void lh::par_copy(lh_handle* h, const ByteSeg* seg, int nseg) {
+    const size_t blk = 262144;
+    size_t total = 0;
+    for (int k = 0; k < nseg; ++k) total += (seg[k].dst && seg[k].src) ? seg[k].n : 0;
+    if (total < 4 * blk) {   // waking the pool costs more than copying a small call's bytes
+        for (int k = 0; k < nseg; ++k)
+            if (seg[k].dst && seg[k].src && seg[k].n) std::memcpy(seg[k].dst, seg[k].src, seg[k].n);
+        return;
+    }
+    std::vector<std::pair<int, size_t>> jobs;
+    for (int k = 0; k < nseg; ++k)
+        if (seg[k].dst && seg[k].src)
+            for (size_t o = 0; o < seg[k].n; o += blk) jobs.emplace_back(k, o);
+    auto job = [&](int j) {
+        const ByteSeg& g = seg[jobs[j].first];
+        const size_t o = jobs[j].second, c = std::min(blk, g.n - o);
+        std::memcpy((uint8_t*)g.dst + o, (const uint8_t*)g.src + o, c);
+    };
+    if (h->pool && jobs.size() > 1) h->pool->run((int)jobs.size(), job);
+    else for (int j = 0; j < (int)jobs.size(); ++j) job(j);
 }
 
 namespace {
 
-enum { KC_LIN = 0, KC_REDUCE = 1, KC_CTRL = 2, KC_ALLREDUCE = 3, KC_INIT = 4, KC_N = 8 };
 const char* kKernelNames[KC_N] = {"k_lin", "k_reduce", "k_ctrl", "allreduce", "k_lin_init", "", "", ""};
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        const size_t c = std::max<size_t>(count, 1);
-        hipError_t e = hipMalloc(&p, c * sizeof(T));
-        if (e == hipSuccess) n = c;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-// pinned host staging, grown on demand and reused across windows
-// A typed window into an arena (no ownership): the per-window tables share one device and one pinned
-// allocation so they cross the link as one copy (upload_impl)
-template <typename T>
-struct View {
-    T* p = nullptr;
-    size_t n = 0;
-    void release() { p = nullptr; n = 0; }
-};
-template <typename T>
-struct HostBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-        const size_t c = std::max<size_t>(count + count / 4, 1);   // headroom: the next window is similar
-        hipError_t e = hipHostMalloc((void**)&p, c * sizeof(T), hipHostMallocDefault);
-        if (e == hipSuccess) n = c;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-// How the ranks exchange ("One seam"): not at all (one rank), RCCL (also LH_FORCE_RCCL=1 on one rank),
-// LH_COMM_HOST, LH_COMM_P2P.  Decided once in lh_create; only the collective functions switch on it.
-enum Transport { TR_NONE, TR_RCCL, TR_HOST, TR_P2P };
-struct P2pState {
-    DevBuf<double> d_xchg;        // this rank's exchange buffer (lh_common.h), IPC-exported
-    lh_peers peers{};             // every rank's exchange buffer as mapped here (opened IPC handles)
-    long xchg_slot = 0;           // doubles per slot
-    uint32_t solve_gen = 0;       // tags: solves so far (the same count on every rank)
-    int *h_xerr = nullptr, *d_xerr = nullptr;   // host-mapped failure word (a peer's tag did not arrive)
-};
 
 // ---- Eigen quaternion <-> matrix (host copies of the formulas the kernels use) ----
 void q_from_R(const double* R, double q[4]) {
@@ -256,154 +165,11 @@ int auto_host_threads() {
     return std::max(1, std::min(8, n));
 }
 
-}  // namespace
-
-struct lh_handle {
-    lh_options opt;
-    int device = 0;
-    int lds_limit = 160 * 1024;   // hipDeviceAttributeMaxSharedMemoryPerBlock of the device
-    hipStream_t stream = nullptr;
-    Transport transport = TR_NONE;
-    ncclComm_t comm = nullptr;    // TR_RCCL's communicator
-    P2pState p2p;                 // TR_P2P's buffers and counters
-    bool uploaded = false;
-    bool upload_joined = false;   // this upload has taken part in the sharded envelope all-reduce
-    bool upload_tail = false;     // ... and every rank passed it: the upload's closing status all-reduce follows
-    lh::Pool* pool = nullptr;
-
-    // window
-    lh::Plan plan;
-    int P = 0, L = 0, ncam = 1, n_rec = 0;
-    int64_t O = 0, n_slots = 0;
-    lh_params prm{};
-    lh_rs_layout LY{};
-    double last_prep_ms = 0.0, last_upload_ms = 0.0;
-
-    // pinned staging of the upload
-    View<lh_chunk> s_chunks;                                  // the per-window tables: views into s_arena
-    View<lh_subbatch> s_sbs;
-    View<uint32_t> s_items, s_pair_ptr, s_rsmap, s_brow_ent, s_red;
-    View<uint16_t> s_pair_pq;
-    View<uint16_t> s_units;                                   // k_ctrl's work units (lh_ctrl_units)
-    View<uint16_t> s_bunits;                                  // k_ctrl_b's work units
-    View<int32_t> s_bblk;                                     // k_ctrl_b's pair -> block table
-    View<int32_t> s_lm_perm, s_brow_ptr;
-    View<uint64_t> s_fixed;
-    View<double> s_qt, s_ptab, s_ext;
-    HostBuf<uint8_t> s_arena;
-    size_t arena_bytes = 0;
-    HostBuf<uint32_t> s_meta;
-    HostBuf<int32_t> s_obs_perm;
-    HostBuf<float> s_uv;                                     // pixels, 2 floats per slot
-    HostBuf<double> s_lm, s_rs;                              // s_rs: the host-exchange buffer
-    HostBuf<double> s_out;                                   // pinned staging of the download
-    DevBuf<unsigned> d_ocnt;                                 // the outlier pass's per-block counts (ABI 5)
-    DevBuf<uint8_t> d_oflag;                                 // its flags (window order), then threshold and counts
-    DevBuf<double> d_otot;                                   // a sharded pass: this rank's counts, then all ranks' sums
-    HostBuf<uint8_t> s_oflag;                                // pinned staging of the flags
-    hipEvent_t ev_staging = nullptr;   // the upload's last copy out of the staging (reused by the next upload)
-    bool staging_pending = false;
-
-    // device buffers
-    View<lh_chunk> d_chunks;                                  // the per-window tables: views into d_arena
-    View<lh_subbatch> d_sbs;
-    View<uint32_t> d_pair_ptr, d_items, d_rsmap, d_red;
-    int n_red = 0;   // k_reduce's pair blocks (d_red: 4 words each, then the scalar block's sentinel)
-    View<uint16_t> d_pair_pq, d_units, d_bunits;
-    View<int32_t> d_bblk;
-    DevBuf<double> d_band;        // k_ctrl_b's scratch per ladder rung (lh::band_scratch)
-    lh::SolveConfig cfg;          // how the uploaded window is solved (lh::solve_config): the controller kind and its sizes
-    View<int32_t> d_lm_perm;
-    View<double> d_ptab_init, d_qt_init, d_ext;
-    DevBuf<uint8_t> d_arena;
-    DevBuf<uint32_t> d_meta;
-    DevBuf<int32_t> d_obs_perm;
-    DevBuf<float> d_uv;
-    DevBuf<double> d_lm_in, d_rec, d_ptab, d_qt, d_rho, d_rows, d_csc, d_gA, d_gS, d_rs_stage,
-        d_rs_commit, d_maxd, d_dxp, d_out_xyz, d_out_rho;
-    DevBuf<lh_ctrl> d_ctrl;
-    View<uint64_t> d_fixed;      // fixed-pose bits (Plan::fixed_bits)
-    View<int32_t> d_brow_ptr;    // the reduced system's block rows (Plan::brow_ptr / brow_ent, k_ctrl_p)
-    View<uint32_t> d_brow_ent;
-    DevBuf<uint8_t> d_wflag;     // [2][n_slots] inlier flags of each state buffer's linearisation (k_lin)
-    DevBuf<double> d_img;        // [2][LH_IMG_SZ] k_ctrl's LDS system image, staged / committed (prm.img)
-    // frontend pose-only batch (lh_estimate_pose)
-    // inputs and outputs each packed into one arena, so a call is one upload and one download
-    // through pinned staging (a single frame is latency-bound: every extra copy costs ~10 us)
-    DevBuf<uint8_t> f_in, f_out;
-    DevBuf<double> f_res;
-    HostBuf<uint8_t> s_fin, s_fout;
-    // LK optical flow (lh_lk_track): both images' pyramids, keypoints
-    DevBuf<uint8_t> k_img[2], k_succ;
-    DevBuf<float> k_kp1, k_kp2;
-    // triangulation (lh_triangulate, lh_stereo_landmarks): the inputs packed into one arena, the outputs into another
-    DevBuf<uint8_t> t_in, t_out;
-    // feature detection (lh_detect_features): image, allow and state bytes; lambda; candidate and corner lists
-    DevBuf<uint8_t> g_img, g_allow, g_state;
-    DevBuf<double> g_eig, g_acc_lam, g_resp;
-    DevBuf<uint32_t> g_cand, g_acc_idx;
-    DevBuf<float> g_excl, g_kp;
-    DevBuf<lh_gftt_ctl> g_ctl;
-    HostBuf<lh_gftt_ctl> s_gctl;   // pinned: read back once per batch of selection rounds
-    lh_ctrl* h_ctrl = nullptr;   // pinned
-    int last_chains = -1;        // lh_debug_chains: the last synchronous solve's stop chain
-    int last_lskips = -1;        // lh_debug_ladder: its rejections onto a built ladder rung
-    int last_batches = -1;       // lh_debug_batch: its batches of evaluate-only rungs
-    int last_retrials[2] = {-1, -1};   // lh_debug_batch: their acceptances (re-run; re-run and stopping)
-    size_t rho_off = 0;          // the last solve's per-edge rho0 "as last evaluated": its rung buffer in d_rho (a batch)
-    int* h_done = nullptr;       // pinned, mapped lh_host_words: [0] k_ctrl raises it when the LM loop stops, [1] progress
-                                 // word 2 * (last live trial) + (one iteration from max_iters)
-    int* d_done = nullptr;       // device alias of h_done
-
-    // per-solve bookkeeping
-    int64_t n_coll = 0;          // data-path all-reduces of the last solve
-
-    // profiling
-    struct PendingEv { int kc; int trial; hipEvent_t a, b; };
-    std::vector<PendingEv> pending;
-    int cur_trial = 0;
-    std::vector<hipEvent_t> event_pool;
-    size_t event_next = 0;
-    int64_t launches[KC_N] = {0};
-    double total_ms[KC_N] = {0};
-};
-
-namespace {
-
-bool g_debug = getenv("LH_DEBUG") != nullptr;
-
-#define HIPCHK(x)                                                                                        \
-    do {                                                                                                 \
-        hipError_t e_ = (x);                                                                             \
-        if (e_ != hipSuccess) {                                                                          \
-            if (g_debug) fprintf(stderr, "lego_ba: %s failed: %s\n", #x, hipGetErrorString(e_));       \
-            return LH_E_HIP;                                                                             \
-        }                                                                                                \
-    } while (0)
-
-#define NCCLCHK(x)                                                                                       \
-    do {                                                                                                 \
-        ncclResult_t r_ = (x);                                                                           \
-        if (r_ != ncclSuccess) {                                                                         \
-            if (g_debug) fprintf(stderr, "lego_ba: %s failed: %s\n", #x, ncclGetErrorString(r_));      \
-            return LH_E_RCCL;                                                                            \
-        }                                                                                                \
-    } while (0)
-
 // What other sites ask of the transport: is the solve sharded; does it exchange one trial at a time on the host
 // (every rank reading the device's stop flag at the same point); has it failed (P2P: a peer's tag did not arrive)
 bool sharded(const lh_handle* h) { return h->transport != TR_NONE; }
 bool exchange_synchronous(const lh_handle* h) { return h->transport == TR_HOST; }
 bool transport_failed(const lh_handle* h) { return h->transport == TR_P2P && *h->p2p.h_xerr; }
-
-hipEvent_t next_event(lh_handle* h) {
-    if (h->event_next == h->event_pool.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        h->event_pool.push_back(e);
-    }
-    return h->event_pool[h->event_next++];
-}
 
 struct Prof {
     lh_handle* h;
@@ -457,30 +223,6 @@ void copy_slots(void* user, int64_t s0, int64_t s1) {
     if (e == hipSuccess)
         e = hipMemcpyAsync(h->d_obs_perm.p + s0, h->s_obs_perm.p + s0, n * sizeof(int32_t), hipMemcpyHostToDevice, st);
     c->err = e;
-}
-
-// host copies between caller memory and pinned staging, in ~256 KB blocks over the planner's pool
-struct ByteSeg { void* dst; const void* src; size_t n; };
-void par_copy(lh_handle* h, const ByteSeg* seg, int nseg) {
-    const size_t blk = 262144;
-    size_t total = 0;
-    for (int k = 0; k < nseg; ++k) total += (seg[k].dst && seg[k].src) ? seg[k].n : 0;
-    if (total < 4 * blk) {   // waking the pool costs more than copying a small call's bytes
-        for (int k = 0; k < nseg; ++k)
-            if (seg[k].dst && seg[k].src && seg[k].n) std::memcpy(seg[k].dst, seg[k].src, seg[k].n);
-        return;
-    }
-    std::vector<std::pair<int, size_t>> jobs;
-    for (int k = 0; k < nseg; ++k)
-        if (seg[k].dst && seg[k].src)
-            for (size_t o = 0; o < seg[k].n; o += blk) jobs.emplace_back(k, o);
-    auto job = [&](int j) {
-        const ByteSeg& g = seg[jobs[j].first];
-        const size_t o = jobs[j].second, c = std::min(blk, g.n - o);
-        std::memcpy((uint8_t*)g.dst + o, (const uint8_t*)g.src + o, c);
-    };
-    if (h->pool && jobs.size() > 1) h->pool->run((int)jobs.size(), job);
-    else for (int j = 0; j < (int)jobs.size(); ++j) job(j);
 }
 
 // Wait for an event by polling it: hipEventSynchronize measured ~2 ms for lh_upload's copies that the
@@ -537,12 +279,6 @@ int upload_impl(lh_handle* h, const lh_window* w, bool sync) {
 
 // ---- the stages of an upload, in upload_body's order.  None of them decides how the window is solved:
 //      that is lh::solve_config (lh_plan.h), whose result the handle keeps (h->cfg). ----
-#define STAGE(x)                                                                                         \
-    do {                                                                                                 \
-        const int st_ = (x);                                                                             \
-        if (st_ != LH_OK) return st_;                                                                    \
-    } while (0)
-
 // the previous upload's copies out of the pinned staging
 int wait_staging(lh_handle* h) {
     if (h->staging_pending) {
@@ -1277,17 +1013,12 @@ int rank_max(lh_handle* h, double* buf, int n) {
         case TR_RCCL: break;
     }
     DevBuf<double> d;
-    auto run = [&]() -> int {
-        HIPCHK(d.ensure(n));
-        HIPCHK(hipMemcpyAsync(d.p, buf, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        NCCLCHK(ncclAllReduce(d.p, d.p, n, ncclFloat64, ncclMax, h->comm, h->stream));
-        HIPCHK(hipMemcpyAsync(buf, d.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return LH_OK;
-    };
-    const int st = run();
-    d.release();
-    return st;
+    HIPCHK(d.ensure(n));
+    HIPCHK(hipMemcpyAsync(d.p, buf, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NCCLCHK(ncclAllReduce(d.p, d.p, n, ncclFloat64, ncclMax, h->comm, h->stream));
+    HIPCHK(hipMemcpyAsync(buf, d.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return LH_OK;
 }
 
 // every peer's mapping closed (this rank's own entry is its buffer, not a mapping)
@@ -1514,34 +1245,17 @@ int lh_create(lh_handle** hp, const lh_options* opt) {
     return LH_OK;
 }
 
+// What depends on order (also of a handle lh_create gave up on half-built); `delete h` frees the handle's buffers
 void lh_destroy(lh_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm) ncclCommDestroy(h->comm);
-    p2p_close_peers(h->p2p); h->p2p.d_xchg.release();
-    if (h->p2p.h_xerr) (void)hipHostFree(h->p2p.h_xerr);
+    p2p_close_peers(h->p2p);   // the peers' mappings, while this rank's own exchange buffer is still there
     for (auto e : h->event_pool) (void)hipEventDestroy(e);
-    delete h->pool;
-    h->f_in.release(); h->f_out.release(); h->f_res.release(); h->s_fin.release(); h->s_fout.release();
-    h->k_img[0].release(); h->k_img[1].release(); h->k_succ.release(); h->k_kp1.release(); h->k_kp2.release();
-    h->t_in.release(); h->t_out.release();
-    h->g_img.release(); h->g_allow.release(); h->g_state.release(); h->g_eig.release(); h->g_acc_lam.release();
-    h->g_resp.release(); h->g_cand.release(); h->g_acc_idx.release(); h->g_excl.release(); h->g_kp.release();
-    h->g_ctl.release(); h->s_gctl.release();
-    h->d_chunks.release(); h->d_sbs.release(); h->d_meta.release(); h->d_obs_perm.release(); h->d_lm_perm.release();
-    h->d_pair_ptr.release(); h->d_items.release(); h->d_pair_pq.release(); h->d_lm_in.release();
-    h->d_uv.release(); h->d_rec.release(); h->d_ptab.release(); h->d_out_xyz.release(); h->d_out_rho.release();
-    h->d_ptab_init.release(); h->d_qt.release(); h->d_qt_init.release(); h->d_ext.release(); h->d_rho.release();
-    h->d_rows.release(); h->d_csc.release(); h->d_gA.release(); h->d_gS.release(); h->d_rs_stage.release(); h->d_rs_commit.release(); h->d_rsmap.release(); h->d_maxd.release(); h->d_band.release();
-    h->d_dxp.release(); h->d_ctrl.release(); h->d_wflag.release(); h->d_img.release(); h->d_fixed.release();
-    h->d_brow_ptr.release(); h->d_brow_ent.release(); h->d_arena.release(); h->s_arena.release();
-    h->s_chunks.release(); h->s_sbs.release(); h->s_meta.release(); h->s_items.release(); h->s_pair_ptr.release();
-    h->s_rsmap.release(); h->s_pair_pq.release(); h->s_obs_perm.release(); h->s_lm_perm.release(); h->s_uv.release();
-    h->s_lm.release(); h->s_qt.release(); h->s_ptab.release(); h->s_ext.release(); h->s_rs.release();
-    h->s_out.release();
-    h->d_ocnt.release(); h->d_oflag.release(); h->s_oflag.release(); h->d_otot.release();
     if (h->ev_staging) (void)hipEventDestroy(h->ev_staging);
+    delete h->pool;
+    if (h->p2p.h_xerr) (void)hipHostFree(h->p2p.h_xerr);
     if (h->h_ctrl) (void)hipHostFree(h->h_ctrl);
     if (h->h_done) (void)hipHostFree(h->h_done);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1600,450 +1314,6 @@ int lh_set_profiling(lh_handle* h, int on) {
 void lh_kernel_stats_reset(lh_handle* h) {
     if (!h) return;
     for (int i = 0; i < KC_N; ++i) { h->launches[i] = 0; h->total_ms[i] = 0.0; }
-}
-
-// Frontend::EstimateCurrentPose for a batch of frames (frontend_lego.cpp:157-250): upload, one
-// k_frames launch (one workgroup per frame), download.
-static int estimate_pose_impl(lh_handle* h, const lh_frames* in, lh_frames_result* out) {
-    if (!h || !in || !out) return LH_E_BADARG;
-    const int F = in->n_frames;
-    if (F < 0 || (F > 0 && (!in->obs_ptr || !in->pose_Tcw))) return LH_E_BADARG;
-    if (F == 0) { out->time_ms = 0.0; return LH_OK; }
-    if (in->obs_ptr[0] != 0) return LH_E_BADARG;
-    for (int f = 0; f < F; ++f)
-        if (in->obs_ptr[f + 1] < in->obs_ptr[f] || in->obs_ptr[f + 1] - in->obs_ptr[f] > (int64_t)INT32_MAX)
-            return LH_E_BADARG;
-    const int64_t O = in->obs_ptr[F];
-    if (O > 0 && (!in->pts_w || !in->obs_uv)) return LH_E_BADARG;
-    if (!out->pose_Tcw) return LH_E_BADARG;
-    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
-    hipStream_t s = h->stream;
-    // arena layouts (16-byte aligned segments)
-    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const bool has_flag = in->is_outlier && O > 0;
-    const size_t i_ptr = 0, i_pose = al(sizeof(int64_t) * (F + 1)), i_pts = i_pose + al(sizeof(double) * 12 * (size_t)F),
-                 i_uv = i_pts + al(sizeof(double) * 3 * (size_t)O), i_flag = i_uv + al(sizeof(double) * 2 * (size_t)O),
-                 i_end = i_flag + (has_flag ? al((size_t)O) : 0);
-    const size_t o_pose = 0, o_rchi2 = al(sizeof(double) * 12 * (size_t)F), o_iters = o_rchi2 + al(sizeof(double) * (size_t)O),
-                 o_inl = o_iters + al(sizeof(int32_t) * (size_t)F), o_flag = o_inl + al(sizeof(int32_t) * (size_t)F),
-                 o_end = o_flag + al((size_t)O);
-    HIPCHK(h->f_in.ensure(i_end));
-    HIPCHK(h->f_out.ensure(o_end));
-    HIPCHK(h->f_res.ensure(2 * (size_t)O));
-    HIPCHK(h->s_fin.ensure(i_end));
-    HIPCHK(h->s_fout.ensure(o_end));
-    {
-        uint8_t* st = h->s_fin.p;
-        const ByteSeg seg[5] = {{st + i_ptr, in->obs_ptr, sizeof(int64_t) * (F + 1)},
-                                {st + i_pose, in->pose_Tcw, sizeof(double) * 12 * (size_t)F},
-                                {st + i_pts, in->pts_w, sizeof(double) * 3 * (size_t)O},
-                                {st + i_uv, in->obs_uv, sizeof(double) * 2 * (size_t)O},
-                                {st + i_flag, in->is_outlier, has_flag ? (size_t)O : 0}};
-        par_copy(h, seg, 5);
-    }
-    HIPCHK(hipMemcpyAsync(h->f_in.p, h->s_fin.p, i_end, hipMemcpyHostToDevice, s));
-    uint8_t* fi = h->f_in.p;
-    uint8_t* fo = h->f_out.p;
-    lh_params prm{};
-    prm.max_iters = h->opt.max_iters;
-    prm.max_trials = h->opt.max_trials;
-    prm.strategy = h->opt.strategy;
-    prm.lambda_given = h->opt.lambda_init >= 0.0;
-    prm.gate_mode = h->opt.gate_mode;
-    prm.precision = h->opt.precision;
-    prm.huber_delta = h->opt.huber_delta;
-    prm.stop_dchi2 = h->opt.stop_dchi2;
-    prm.tau = h->opt.tau;
-    prm.lambda_cap = h->opt.lambda_cap;
-    prm.lambda_init = h->opt.lambda_init;
-    for (int i = 0; i < 4; ++i) prm.K[i] = in->K[i];
-    hipEvent_t e0 = next_event(h), e1 = next_event(h);
-    if (!e0 || !e1) return LH_E_HIP;
-    HIPCHK(hipEventRecord(e0, s));
-    HIPCHK(lh_launch_frames(s, F, (const int64_t*)(fi + i_ptr), (const double*)(fi + i_pose),
-                            (const double*)(fi + i_pts), (const double*)(fi + i_uv), has_flag ? fi + i_flag : nullptr,
-                            prm, h->f_res.p, (double*)(fo + o_pose), fo + o_flag, (double*)(fo + o_rchi2),
-                            (int32_t*)(fo + o_iters), (int32_t*)(fo + o_inl)));
-    HIPCHK(hipEventRecord(e1, s));
-    // one download of what the caller asked for: the pose block always, the rest up to the last wanted
-    const size_t want = out->is_outlier && O > 0 ? o_end
-                        : out->n_inliers         ? o_flag
-                        : out->iterations        ? o_inl
-                        : out->edge_chi2 && O > 0 ? o_iters
-                                                 : o_rchi2;
-    HIPCHK(hipMemcpyAsync(h->s_fout.p, fo, want, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    {
-        const uint8_t* st = h->s_fout.p;
-        const ByteSeg seg[5] = {{out->pose_Tcw, st + o_pose, sizeof(double) * 12 * (size_t)F},
-                                {out->edge_chi2, st + o_rchi2, out->edge_chi2 ? sizeof(double) * (size_t)O : 0},
-                                {out->iterations, st + o_iters, out->iterations ? sizeof(int32_t) * (size_t)F : 0},
-                                {out->n_inliers, st + o_inl, out->n_inliers ? sizeof(int32_t) * (size_t)F : 0},
-                                {out->is_outlier, st + o_flag, out->is_outlier ? (size_t)O : 0}};
-        par_copy(h, seg, 5);
-    }
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out->time_ms = ms;
-    h->event_next = 0;
-    return LH_OK;
-}
-
-// LKOpticalFlow4Layer / LKOpticalFlow1Layer (algorithm.cpp:11-206): upload both images, build the
-// pyramids (k_lk_pyr per level and image), track every keypoint (k_lk_track), download.
-// lk_enqueue: everything up to and including the tracking launch, on the handle's stream; *e0 is recorded in
-// front of the first kernel.  kp2 (host): the initial guess when in->has_initial.
-static int lk_enqueue(lh_handle* h, const lh_lk_input* in, const float* kp2, const uint8_t* success, hipEvent_t* e0_out) {
-    if (in->levels != 1 && in->levels != LH_LK_MAX_LEVELS) return LH_E_BADARG;
-    if (in->cols < 1 || in->rows < 1 || in->step < in->cols || in->n_points < 0) return LH_E_BADARG;
-    if (!in->img1 || !in->img2) return LH_E_BADARG;
-    const int n = in->n_points;
-    if (n > 0 && (!in->kp1 || !kp2 || !success)) return LH_E_BADARG;
-    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
-    // level sizes: cv::Size(cols * 0.5, rows * 0.5) truncated (algorithm.cpp:146-153)
-    int cols[LH_LK_MAX_LEVELS], rows[LH_LK_MAX_LEVELS];
-    int64_t step[LH_LK_MAX_LEVELS], off[LH_LK_MAX_LEVELS];
-    cols[0] = in->cols; rows[0] = in->rows; step[0] = in->step; off[0] = 0;
-    int64_t total = (int64_t)in->rows * in->step;
-    for (int l = 1; l < in->levels; ++l) {
-        cols[l] = (int)(cols[l - 1] * 0.5);
-        rows[l] = (int)(rows[l - 1] * 0.5);
-        if (cols[l] < 1 || rows[l] < 1) return LH_E_BADARG;
-        step[l] = cols[l];
-        off[l] = total;
-        total += (int64_t)cols[l] * rows[l];
-    }
-    hipStream_t s = h->stream;
-    HIPCHK(h->k_img[0].ensure((size_t)total));
-    HIPCHK(h->k_img[1].ensure((size_t)total));
-    HIPCHK(h->k_kp1.ensure(2 * (size_t)std::max(n, 1)));
-    HIPCHK(h->k_kp2.ensure(2 * (size_t)std::max(n, 1)));
-    HIPCHK(h->k_succ.ensure((size_t)std::max(n, 1)));
-    // the caller's last row guarantees only `cols` readable bytes (a cv::Mat ROI has step > cols):
-    // copy (rows - 1) * step + cols bytes and zero the rest of that row, which no tap reads as image
-    // data (GetPixelValue's out-of-buffer taps read 0, lh_lk.hip)
-    const size_t img_bytes = (size_t)(in->rows - 1) * (size_t)in->step + (size_t)in->cols;
-    const size_t tail = (size_t)in->rows * (size_t)in->step - img_bytes;
-    for (int im = 0; im < 2; ++im) {
-        HIPCHK(hipMemcpyAsync(h->k_img[im].p, im ? in->img2 : in->img1, img_bytes, hipMemcpyHostToDevice, s));
-        if (tail) HIPCHK(hipMemsetAsync(h->k_img[im].p + img_bytes, 0, tail, s));
-    }
-    if (n > 0) {
-        HIPCHK(hipMemcpyAsync(h->k_kp1.p, in->kp1, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
-        // without an initial guess kp2 is scaled but never read (dx = dy = 0 at the top level)
-        if (in->has_initial) HIPCHK(hipMemcpyAsync(h->k_kp2.p, kp2, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
-        else HIPCHK(hipMemsetAsync(h->k_kp2.p, 0, 2 * sizeof(float) * (size_t)n, s));
-    }
-    lh_lk_levels L[2];
-    for (int im = 0; im < 2; ++im)
-        for (int l = 0; l < LH_LK_MAX_LEVELS; ++l) {
-            const int ll = l < in->levels ? l : 0;
-            L[im].data[l] = h->k_img[im].p + off[ll];
-            L[im].cols[l] = cols[ll];
-            L[im].rows[l] = rows[ll];
-            L[im].step[l] = step[ll];
-        }
-    hipEvent_t e0 = next_event(h);
-    if (!e0) return LH_E_HIP;
-    HIPCHK(hipEventRecord(e0, s));
-    for (int l = 1; l < in->levels; ++l)
-        for (int im = 0; im < 2; ++im)
-            HIPCHK(lh_launch_lk_pyr(s, L[im].data[l - 1], cols[l - 1], rows[l - 1], step[l - 1],
-                                    h->k_img[im].p + off[l], cols[l], rows[l]));
-    HIPCHK(lh_launch_lk_track(s, &L[0], &L[1], in->levels, n, h->k_kp1.p, h->k_kp2.p, h->k_kp2.p, h->k_succ.p,
-                              in->inverse ? 1 : 0, in->has_initial ? 1 : 0));
-    *e0_out = e0;
-    return LH_OK;
-}
-
-static int lk_track_impl(lh_handle* h, const lh_lk_input* in, lh_lk_result* out) {
-    if (!h || !in || !out) return LH_E_BADARG;
-    hipEvent_t e0 = nullptr;
-    if (int st = lk_enqueue(h, in, out->kp2, out->success, &e0)) return st;
-    const int n = in->n_points;
-    hipStream_t s = h->stream;
-    hipEvent_t e1 = next_event(h);
-    if (!e1) return LH_E_HIP;
-    HIPCHK(hipEventRecord(e1, s));
-    if (n > 0) {
-        HIPCHK(hipMemcpyAsync(out->kp2, h->k_kp2.p, 2 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(out->success, h->k_succ.p, (size_t)n, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out->time_ms = ms;
-    h->event_next = 0;
-    return LH_OK;
-}
-
-// legoslam::triangulation (algorithm.h:11-34) for a batch of points (k_triangulate, lh_tri.hip).
-// The fields lh_triangulate and lh_stereo_landmarks share: threshold, gate, T_out, and the output arena
-// (pt [n][3], sing_ratio [n], flags [n]).
-struct TriOut { size_t o_ratio, o_flag, o_end; };
-static int tri_outputs(lh_handle* h, lh_tri_args* a, int n, double thr, int gate, double y_max, double z_min,
-                       double z_max, const double* T_out, TriOut* o) {
-    o->o_ratio = sizeof(double) * 3 * (size_t)n;
-    o->o_flag = o->o_ratio + sizeof(double) * (size_t)n;
-    o->o_end = o->o_flag + (size_t)n;
-    HIPCHK(h->t_out.ensure(o->o_end));
-    a->thr = thr;
-    a->gate = gate ? 1 : 0;
-    a->y_max = y_max; a->z_min = z_min; a->z_max = z_max;
-    a->has_T = T_out ? 1 : 0;
-    for (int i = 0; i < 12; ++i) a->T[i] = T_out ? T_out[i] : 0.0;
-    a->pt = (double*)h->t_out.p;
-    a->ratio = (double*)(h->t_out.p + o->o_ratio);
-    a->flags = h->t_out.p + o->o_flag;
-    return LH_OK;
-}
-
-static int32_t tri_count_accepted(const uint8_t* flags, int n) {
-    int32_t c = 0;
-    for (int i = 0; i < n; ++i) c += flags[i] == 0;
-    return c;
-}
-
-static int triangulate_impl(lh_handle* h, const lh_tri_input* in, lh_tri_result* out) {
-    if (!h || !in || !out) return LH_E_BADARG;
-    const int n = in->n_points, P = in->n_poses;
-    if (n < 0) return LH_E_BADARG;
-    out->n_accepted = 0;
-    out->time_ms = 0.0;
-    if (n == 0) return LH_OK;
-    if (P < 1 || !in->pose_Tcw || !in->view_xy || !out->pt || !out->flags) return LH_E_BADARG;
-    if (in->view_ptr && !in->view_pose) return LH_E_BADARG;
-    int64_t nv;
-    if (in->view_ptr) {
-        if (in->view_ptr[0] < 0) return LH_E_BADARG;
-        for (int i = 0; i < n; ++i)
-            if (in->view_ptr[i + 1] - in->view_ptr[i] < 2) return LH_E_BADARG;   // fewer than 2 views, or decreasing
-        nv = in->view_ptr[n];
-        for (int64_t v = in->view_ptr[0]; v < nv; ++v)
-            if (in->view_pose[v] >= (uint32_t)P) return LH_E_BADARG;
-    } else {
-        if (P < 2) return LH_E_BADARG;
-        nv = (int64_t)n * P;
-    }
-    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
-    hipStream_t s = h->stream;
-    // input arena: doubles first, then the int64 CSR, then the 32-bit pose indices
-    const size_t i_K = sizeof(double) * 12 * (size_t)P;
-    const size_t i_xy = i_K + sizeof(double) * 4 * (size_t)P;
-    const size_t i_ptr = i_xy + sizeof(double) * 2 * (size_t)nv;
-    const size_t i_vp = i_ptr + (in->view_ptr ? sizeof(int64_t) * ((size_t)n + 1) : 0);
-    const size_t i_end = i_vp + (in->view_ptr ? sizeof(uint32_t) * (size_t)nv : 0);
-    HIPCHK(h->t_in.ensure(i_end));
-    uint8_t* ti = h->t_in.p;
-    lh_tri_args a{};
-    TriOut o;
-    if (int st = tri_outputs(h, &a, n, in->sing_ratio_thr, in->gate, in->y_max, in->z_min, in->z_max, in->T_out, &o))
-        return st;
-    HIPCHK(hipMemcpyAsync(ti, in->pose_Tcw, i_K, hipMemcpyHostToDevice, s));
-    if (in->cam_K) HIPCHK(hipMemcpyAsync(ti + i_K, in->cam_K, i_xy - i_K, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ti + i_xy, in->view_xy, i_ptr - i_xy, hipMemcpyHostToDevice, s));
-    if (in->view_ptr) {
-        HIPCHK(hipMemcpyAsync(ti + i_ptr, in->view_ptr, i_vp - i_ptr, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(ti + i_vp, in->view_pose, i_end - i_vp, hipMemcpyHostToDevice, s));
-    }
-    a.n_points = n;
-    a.n_poses = P;
-    a.pose = (const double*)ti;
-    a.cam_K = in->cam_K ? (const double*)(ti + i_K) : nullptr;
-    a.view_xy = (const double*)(ti + i_xy);
-    a.view_ptr = in->view_ptr ? (const int64_t*)(ti + i_ptr) : nullptr;
-    a.view_pose = in->view_ptr ? (const uint32_t*)(ti + i_vp) : nullptr;
-    hipEvent_t e0 = next_event(h), e1 = next_event(h);
-    if (!e0 || !e1) return LH_E_HIP;
-    HIPCHK(hipEventRecord(e0, s));
-    HIPCHK(lh_launch_triangulate(s, &a));
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipMemcpyAsync(out->pt, a.pt, o.o_ratio, hipMemcpyDeviceToHost, s));
-    if (out->sing_ratio) HIPCHK(hipMemcpyAsync(out->sing_ratio, a.ratio, o.o_flag - o.o_ratio, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(out->flags, a.flags, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out->time_ms = ms;
-    out->n_accepted = tri_count_accepted(out->flags, n);
-    h->event_next = 0;
-    return LH_OK;
-}
-
-// lh_lk_track left -> right, then k_triangulate on kp1 / kp2 / success where the tracker left them
-static int stereo_landmarks_impl(lh_handle* h, const lh_stereo_input* in, lh_stereo_result* out) {
-    if (!h || !in || !out) return LH_E_BADARG;
-    const int n = in->lk.n_points;
-    if (!in->pose_Tcw || (n > 0 && (!out->pt || !out->flags))) return LH_E_BADARG;
-    out->n_accepted = 0;
-    hipEvent_t e0 = nullptr;
-    if (int st = lk_enqueue(h, &in->lk, out->kp2, out->success, &e0)) return st;
-    hipStream_t s = h->stream;
-    const size_t i_K = sizeof(double) * 12 * 2, i_end = i_K + sizeof(double) * 4 * 2;
-    HIPCHK(h->t_in.ensure(i_end));
-    uint8_t* ti = h->t_in.p;
-    lh_tri_args a{};
-    TriOut o;
-    if (int st = tri_outputs(h, &a, n, in->sing_ratio_thr, in->gate, in->y_max, in->z_min, in->z_max, in->T_out, &o))
-        return st;
-    HIPCHK(hipMemcpyAsync(ti, in->pose_Tcw, i_K, hipMemcpyHostToDevice, s));
-    if (in->cam_K) HIPCHK(hipMemcpyAsync(ti + i_K, in->cam_K, i_end - i_K, hipMemcpyHostToDevice, s));
-    a.n_points = n;
-    a.n_poses = 2;
-    a.pose = (const double*)ti;
-    a.cam_K = in->cam_K ? (const double*)(ti + i_K) : nullptr;
-    a.kp1 = h->k_kp1.p;
-    a.kp2 = h->k_kp2.p;
-    a.success = h->k_succ.p;
-    HIPCHK(lh_launch_triangulate(s, &a));
-    hipEvent_t e1 = next_event(h);
-    if (!e1) return LH_E_HIP;
-    HIPCHK(hipEventRecord(e1, s));
-    if (n > 0) {
-        HIPCHK(hipMemcpyAsync(out->kp2, h->k_kp2.p, 2 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(out->success, h->k_succ.p, (size_t)n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(out->pt, a.pt, o.o_ratio, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(out->flags, a.flags, (size_t)n, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out->time_ms = ms;
-    out->n_accepted = tri_count_accepted(out->flags, n);
-    h->event_next = 0;
-    return LH_OK;
-}
-
-// Frontend::DetectFeatures (frontend_lego.cpp:292-310): the mask's exclusion boxes, then cv::GFTTDetector's
-// corners, defined in exact arithmetic (lh_gftt.h).  The image, lambda and every list stay on
-// the device; the host reads one lh_gftt_ctl per batch of selection rounds, to know when none is left open.
-#define LH_GFTT_ROUND_BATCH 8   // a round that finds nothing open costs a launch; a check costs a synchronise
-static int detect_features_impl(lh_handle* h, const lh_detect_input* in, lh_detect_result* out) {
-    if (!h || !in || !out || !in->img) return LH_E_BADARG;
-    const int cols = in->cols, rows = in->rows;
-    if (cols < 3 || rows < 3 || in->step < cols || (int64_t)rows * cols > INT32_MAX) return LH_E_BADARG;
-    if (in->mask && in->mask_step < cols) return LH_E_BADARG;
-    if (in->n_exclude < 0 || (in->n_exclude > 0 && !in->exclude_pt)) return LH_E_BADARG;
-    if (out->kp_capacity < 0 || (out->kp_capacity > 0 && !out->kp)) return LH_E_BADARG;
-    if (in->max_corners > 0 && out->kp_capacity < in->max_corners) return LH_E_BADARG;
-    if (!(in->quality_level >= 0.0) || !(in->min_distance >= 0.0)) return LH_E_BADARG;
-    out->n_corners = out->n_candidates = 0;
-    out->lambda_max = 0.0;
-    out->time_ms = 0.0;
-    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
-    hipStream_t s = h->stream;
-    const size_t px = (size_t)rows * (size_t)cols;
-    const int limit = in->max_corners > 0 ? in->max_corners : out->kp_capacity;
-    HIPCHK(h->g_img.ensure(px));
-    HIPCHK(h->g_allow.ensure(px));
-    HIPCHK(h->g_state.ensure(px + 4));   // k_gftt_round reads it by aligned words
-    HIPCHK(h->g_eig.ensure(px));
-    HIPCHK(h->g_cand.ensure(px));
-    HIPCHK(h->g_acc_idx.ensure(px));
-    HIPCHK(h->g_acc_lam.ensure(px));
-    HIPCHK(h->g_excl.ensure(2 * (size_t)std::max(in->n_exclude, 1)));
-    HIPCHK(h->g_kp.ensure(2 * (size_t)std::max(limit, 1)));
-    HIPCHK(h->g_resp.ensure((size_t)std::max(limit, 1)));
-    HIPCHK(h->g_ctl.ensure(1));
-    HIPCHK(h->s_gctl.ensure(1));
-    // rows packed to `cols` bytes: only `cols` bytes of a caller's row are readable (a cv::Mat ROI has step > cols)
-    auto upload_rows = [&](uint8_t* dst, const uint8_t* src, int64_t step) {
-        if (step == cols) return hipMemcpyAsync(dst, src, px, hipMemcpyHostToDevice, s);
-        return hipMemcpy2DAsync(dst, (size_t)cols, src, (size_t)step, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice, s);
-    };
-    HIPCHK(upload_rows(h->g_img.p, in->img, in->step));
-    if (in->mask)
-        HIPCHK(upload_rows(h->g_allow.p, in->mask, in->mask_step));
-    else
-        HIPCHK(hipMemsetAsync(h->g_allow.p, 1, px, s));
-    if (in->n_exclude > 0)
-        HIPCHK(hipMemcpyAsync(h->g_excl.p, in->exclude_pt, 2 * sizeof(float) * (size_t)in->n_exclude, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(h->g_ctl.p, 0, sizeof(lh_gftt_ctl), s));
-    lh_gftt_args a{};
-    a.cols = cols; a.rows = rows;
-    a.img = h->g_img.p; a.allow = h->g_allow.p;
-    a.n_exclude = in->n_exclude; a.exclude_pt = h->g_excl.p; a.exclude_half = in->exclude_half;
-    a.quality = in->quality_level;
-    a.min_dist2 = in->min_distance * in->min_distance;
-    // candidates nearer than min_distance differ by at most ceil(min_distance) - 1 pixels along an axis
-    a.reach = in->min_distance < 1.0 ? -1 : (int)std::min(std::ceil(in->min_distance) - 1.0, (double)std::max(cols, rows));
-    a.limit = limit;
-    a.eig = h->g_eig.p; a.state = h->g_state.p; a.cand = h->g_cand.p;
-    a.acc_idx = h->g_acc_idx.p; a.acc_lam = h->g_acc_lam.p;
-    a.kp = h->g_kp.p; a.response = h->g_resp.p; a.ctl = h->g_ctl.p;
-    hipEvent_t e0 = next_event(h), e1 = next_event(h);
-    if (!e0 || !e1) return LH_E_HIP;
-    HIPCHK(hipEventRecord(e0, s));
-    HIPCHK(lh_launch_gftt_front(s, &a));
-    const lh_gftt_ctl& ctl = *h->s_gctl.p;
-    if (a.reach >= 0)
-        for (int r = 0;; r += LH_GFTT_ROUND_BATCH) {   // a round decides at least the strongest open candidate
-            HIPCHK(lh_launch_gftt_rounds(s, &a, r, LH_GFTT_ROUND_BATCH));
-            HIPCHK(hipMemcpyAsync(h->s_gctl.p, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (ctl.open[(r + LH_GFTT_ROUND_BATCH - 1) % 3] == 0) break;
-        }
-    HIPCHK(lh_launch_gftt_order(s, &a));
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipMemcpyAsync(h->s_gctl.p, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    if (out->eig) HIPCHK(hipMemcpyAsync(out->eig, a.eig, sizeof(double) * px, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int64_t n_written = std::min<int64_t>(ctl.n_acc, limit);
-    if (n_written > 0) {
-        HIPCHK(hipMemcpyAsync(out->kp, a.kp, 2 * sizeof(float) * (size_t)n_written, hipMemcpyDeviceToHost, s));
-        if (out->response)
-            HIPCHK(hipMemcpyAsync(out->response, a.response, sizeof(double) * (size_t)n_written, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out->time_ms = ms;
-    out->n_corners = in->max_corners > 0 ? (int32_t)n_written : (int32_t)ctl.n_acc;
-    out->n_candidates = (int32_t)ctl.n_cand;
-    out->lambda_max = ctl.max_key ? lh_gftt_unkey(ctl.max_key) : 0.0;
-    h->event_next = 0;
-    return LH_OK;
-}
-
-// the staging copies build std::vectors (par_copy): no exception crosses the ABI
-int lh_estimate_pose(lh_handle* h, const lh_frames* in, lh_frames_result* out) {
-    try {
-        return estimate_pose_impl(h, in, out);
-    } catch (...) {
-        return LH_E_HIP;
-    }
-}
-
-int lh_lk_track(lh_handle* h, const lh_lk_input* in, lh_lk_result* out) {
-    try {
-        return lk_track_impl(h, in, out);
-    } catch (...) {
-        return LH_E_HIP;
-    }
-}
-
-int lh_triangulate(lh_handle* h, const lh_tri_input* in, lh_tri_result* out) {
-    try {
-        return triangulate_impl(h, in, out);
-    } catch (...) {
-        return LH_E_HIP;
-    }
-}
-
-int lh_stereo_landmarks(lh_handle* h, const lh_stereo_input* in, lh_stereo_result* out) {
-    try {
-        return stereo_landmarks_impl(h, in, out);
-    } catch (...) {
-        return LH_E_HIP;
-    }
-}
-
-int lh_detect_features(lh_handle* h, const lh_detect_input* in, lh_detect_result* out) {
-    try {
-        return detect_features_impl(h, in, out);
-    } catch (...) {
-        return LH_E_HIP;
-    }
 }
 
 int lh_classify_outliers(const double* rchi2, int64_t n_obs, double chi2_th, uint8_t* is_outlier, double* th_out,

@@ -17,7 +17,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "lh_common.h"
+#include "lh_launch.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 

@@ -15,7 +15,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "lh_lk.h"
+#include "lh_launch.h"
 
 #pragma clang fp contract(off)
 

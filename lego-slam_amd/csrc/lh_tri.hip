@@ -11,7 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #define LH_TRI_IMPL
-#include "lh_tri.h"
+#include "lh_launch.h"
 
 #define TRI_BLOCK 64   // one wave per workgroup: frontend batches (~2000 points) then spread over 32 CUs
 

@@ -28,7 +28,7 @@ def timed(name, call):
         wall.append((time.perf_counter() - t0) * 1e3)
         dev.append(r["time_ms"])
     print(f"{name:<58} time_ms median {np.median(dev):8.4f} (min {min(dev):.4f}, max {max(dev):.4f})   "
-          f"wall ms median {np.median(wall):8.3f}")
+          f"wall ms median {np.median(wall):8.3f} (min {min(wall):.3f}, max {max(wall):.3f})")
     return r
 
 
