@@ -120,7 +120,7 @@ void q_mul(const double* a, const double* b, double o[4]) {
     o[0] = w; o[1] = x; o[2] = y; o[3] = z;
 }
 
-// host mirror of d_pose_table (lh_kernels.hip): estimate_ -> (q_T, t_T, ext*T, R_T)
+// host mirror of d_pose_table (lh_edge.h): estimate_ -> (q_T, t_T, ext*T, R_T)
 void pose_table(const double* T12, const double* e, double* pt) {
     const double R[9] = {T12[0], T12[1], T12[2], T12[4], T12[5], T12[6], T12[8], T12[9], T12[10]};
     double q[4];

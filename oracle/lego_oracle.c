@@ -415,7 +415,7 @@ typedef struct {
     int64_t *lm_cnt;         /* edges per landmark (degenerate_guard) */
 } prob_t;
 
-/* degenerate_guard 1: the solver's test (lh_kernels.hip k_lin): fewer than two edges, or a Cholesky
+/* degenerate_guard 1: the solver's test (lh_lin.hip k_lin): fewer than two edges, or a Cholesky
    pivot of H_ll that is not positive */
 static int hll_degenerate(const prob_t *pb, int32_t l, const double *H) {
     if (pb->lm_cnt[l] < 2) return 1;

@@ -1,8 +1,8 @@
-"""Summarise hipcc's -Rpass-analysis=kernel-resource-usage remarks for lh_kernels.hip and fail
+"""Summarise hipcc's -Rpass-analysis=kernel-resource-usage remarks for the kernel files and fail
 (exit 1) if any kernel uses scratch (a register spill): DESIGN.md states every solver kernel is
 spill-free, and the Makefile runs this on every build.
 
-usage: python3 scripts/resource_check.py lego-slam_amd/lib/lh_kernels.resource.txt [lh_lk.resource.txt ...]
+usage: python3 scripts/resource_check.py lego-slam_amd/lib/lh_lin.resource.txt [lh_kernels.resource.txt ...]
 """
 import re
 import subprocess
