@@ -1,5 +1,5 @@
 // lh_dev.h — device helpers shared by every kernel file of the sliding-window BA solver (gfx950).
-// (lh_lin.hip, lh_kernels.hip, lh_frames.hip, lh_aux.hip).
+// (lh_lin.hip, lh_kernels.hip with its headers lh_lm.h and lh_ldlt.h, lh_frames.hip, lh_aux.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

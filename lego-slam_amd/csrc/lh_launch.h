@@ -1,4 +1,4 @@
-// lh_launch.h — the one declaration of every kernel launcher.  The definitions (lh_lin.hip, lh_kernels.hip, lh_frames.hip,
+// lh_launch.h — the one declaration of every kernel launcher.  The definitions (lh_lin.hip, lh_kernels.hip and its lh_probe.hip, lh_frames.hip,
 // lh_aux.hip, lh_lk.hip, lh_tri.hip, lh_gftt.hip) and the callers (lh_host.cpp, lh_frontend.cpp) all include it: the symbols are extern "C", so only
 // the compiler, seeing a definition beside this declaration, can tell that the two sides disagree.
 // (lh_tri.h and lh_gftt.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.)

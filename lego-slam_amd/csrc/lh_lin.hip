@@ -4,7 +4,7 @@
 //             there (residual, SE(3)/point Jacobians, Huber weights, H_pp, H_pl,
 //             H_ll, b), eliminate the landmarks (Schur) — the landmark part as
 //             an f64 MFMA SYRK over a chunk window — and emit one slab per chunk.
-// k_reduce and the controllers (lh_kernels.hip) follow.  Every reduction has a fixed order, so a solve is bitwise
+// k_reduce and the controllers (lh_kernels.hip and the files it includes) follow.  Every reduction has a fixed order, so a solve is bitwise
 // reproducible.
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,4 +1,5 @@
-// lh_probe.hip — test probes: the controllers' solves on a given system, the f64 MFMA lane layout.
+// lh_probe.hip — test probes: the controllers' solves (lh_ldlt.h, lh_ctrl_g.hip) on a given system, the f64 MFMA
+// lane layout.
 // Not a unit of its own: lh_kernels.hip includes it (see there).
 
 extern "C" {

@@ -7,7 +7,7 @@
 //   [4] a dependent f64 FMA chain, per FMA x 100
 //   [5] a dependent v_rcp_f64 -> FMA chain, per pair x 100
 //   [6] a dependent 64-bit DPP row_newbcast -> FMA chain, per pair x 100
-#include "../csrc/lh_kernels.hip"
+#include "../csrc/lh_ldlt.h"
 #include <cstdio>
 #include <vector>
 

@@ -2,7 +2,7 @@
 
 It returns as soon as the host sees the device's stop flag and reads the summary and the trace from
 mapped host memory: the stop trial's controller copies them there from lh_ctrl on one thread and
-raises done behind that thread's system-scope fence (publish_stop in lh_kernels.hip).  Nothing else
+raises done behind that thread's system-scope fence (publish_stop in lh_lm.h).  Nothing else
 checks those words: bench.py replays one window, so a stale or torn summary would look like a correct
 one there.  Here the array-free solve alternates between windows (and between handles whose solves
 stop at different trials) and every scalar and trace entry must equal the synchronous path's (the
