@@ -21,6 +21,7 @@
  *                                                                  or lh_classify_outliers (host, on edge_robust_chi2)
  *     Frontend::EstimateCurrentPose frontend_lego.cpp:157-250 lh_estimate_pose (batched)
  *     LKOpticalFlow4Layer / 1Layer  algorithm.cpp:11-206      lh_lk_track
+ *     cv::calcOpticalFlowPyrLK      frontend_lego.cpp:383-463 lh_klt_track, lh_klt_stereo_landmarks (the live trackers)
  *     triangulation                 algorithm.h:11-34         lh_triangulate (batched)
  *     Frontend::TriangulateNewPoints frontend_lego.cpp:111-155 lh_stereo_landmarks (LK left -> right + triangulation,
  *     Frontend::BuildInitMap        frontend_lego.cpp:323-362                       one call per stereo frame)
@@ -376,6 +377,86 @@ typedef struct lh_stereo_result {
     double time_ms;             /* device time: pyramid + tracking + triangulation (copies excluded) */
 } lh_stereo_result;
 int lh_stereo_landmarks(lh_handle *h, const lh_stereo_input *in, lh_stereo_result *out);
+
+/*
+ * Pyramidal KLT tracking, replacing the call the live frontend makes twice per frame
+ * (Frontend::TrackLastFrameLKOpticalFlowOpenCV and FindFeaturesInRightLKOpticalFlowOpenCV, src/frontend_lego.cpp:383-463):
+ *   cv::calcOpticalFlowPyrLK(img1, img2, kps1, kps2, status, err, cv::Size(11, 11), 3,
+ *                            TermCriteria(COUNT + EPS, 30, 0.01), OPTFLOW_USE_INITIAL_FLOW)
+ * The window is 11 x 11, the images 8-bit gray.  The tracker is defined here, after OpenCV 4's scalar path
+ * (lkpyramid.cpp), in arithmetic that leaves nothing to a compiler or a SIMD width: "float" is IEEE binary32, every
+ * float operation below is one correctly rounded operation, and no product and sum is contracted into an FMA.
+ * OpenCV's own float sums run in SIMD order, so parity with OpenCV itself is not specified to the bit and is
+ * unverified (DESIGN.md 2.5c lists where the two can differ).
+ *
+ *   pyramid      level 0 is the image; level l+1 has size ((cols+1)/2, (rows+1)/2) and
+ *                  dst(x, y) = (sum_{i,j=-2..2} w_i w_j src(r(2x+i), r(2y+j)) + 128) >> 8,  w = (1, 4, 6, 4, 1),
+ *                r = BORDER_REFLECT_101.  Level l+1 is built while l < max_level and both its sizes are > 11
+ *                (buildOpticalFlowPyramid); L is the last level.  Both images get the same pyramid.
+ *   reads        I (img1) and J (img2) outside the image return the REFLECT_101 pixel (offsets reach 11 past an edge).
+ *   derivatives  of I, Scharr, REFLECT_101 neighbours at the edge:
+ *                  t0(x,y) = 3 (I(x,y-1) + I(x,y+1)) + 10 I(x,y),  Ix(x,y) = t0(x+1,y) - t0(x-1,y)
+ *                  t1(x,y) = I(x,y+1) - I(x,y-1),                  Iy(x,y) = 3 (t1(x-1,y) + t1(x+1,y)) + 10 t1(x,y)
+ *                A derivative read at a position outside the image is 0 (the BORDER_CONSTANT border of the buffer).
+ *   per point    status = 1, kp2 = the guess (kp1 without has_initial).  For l = L down to 0, sc = (float)(1 / 2^l):
+ *                p = kp1 sc;  q = kp2 sc if l = L, else 2 kp2;  kp2 = q.  "fail": status = 0 if l = 0; next level.
+ *     1  p -= 5;  ip = floor(p);  !(ip.x >= -11 && ip.x < cols_l && ip.y >= -11 && ip.y < rows_l), in float: fail
+ *     2  weights of (p, ip):  a = p.x - ip.x, b = p.y - ip.y,  w00 = rint(((1-a)(1-b)) 16384),  w01 = rint((a (1-b)) 16384),
+ *        w10 = rint(((1-a) b) 16384) (half to even),  w11 = 16384 - w00 - w01 - w10
+ *     3  for the 121 window pixels (x, y = 0..10), bil(F) = F(ip+(x,y)) w00 + F(ip+(x+1,y)) w01 + F(ip+(x,y+1)) w10 +
+ *        F(ip+(x+1,y+1)) w11:  Iw = (bil(I) + 256) >> 9,  ix = (bil(Ix) + 8192) >> 14,  iy = (bil(Iy) + 8192) >> 14
+ *     4  S11 = sum ix ix, S12 = sum ix iy, S22 = sum iy iy (exact);  A11 = (float)(double)S11 2^-20, A12, A22 likewise;
+ *        D = A11 A22 - A12 A12;  d = A11 - A22;  minEig = ((A22 + A11) - sqrt(d d + (4 A12) A12)) / 242;
+ *        (double)minEig < min_eig_threshold or D < FLT_EPSILON: fail.  D = 1 / D
+ *     5  q -= 5;  prev = 0.  For j = 0 .. max_iters - 1:
+ *        1  iq = floor(q);  the range test of 1: if it fails, status = 0 if l = 0, and the loop ends
+ *        2  weights of (q, iq);  Jw = (bil(J) + 256) >> 9;  diff = Jw - Iw
+ *        3  B1 = sum diff ix, B2 = sum diff iy (exact, in 64 bits);  b1 = (float)(double)B1 2^-20, b2 likewise
+ *        4  delta = ((A12 b2 - A22 b1) D, (A12 b1 - A11 b2) D)
+ *        5  q += delta;  kp2 = q + 5
+ *        6  in double, delta.x^2 + delta.y^2 <= epsilon^2: the loop ends
+ *        7  j > 0 and (double)|delta.x + prev.x| < 0.01 and (double)|delta.y + prev.y| < 0.01 (the sums in float):
+ *           kp2 -= 0.5 delta, and the loop ends
+ *        8  prev = delta
+ * The err output of OpenCV is not computed (the reference discards it).  status is cleared at level 0 only, and a
+ * tracked point may lie outside the image with status 1, both as in OpenCV.  A NaN or infinite keypoint or guess gives
+ * success 0 and is no error.  out->kp2 holds the guess on entry with has_initial; kp2, success and time_ms are
+ * lh_lk_track's.
+ *
+ * LH_E_BADARG: cols < 12 or rows < 12, step < cols, max_level outside 0..3, max_iters < 1, an epsilon that is not > 0,
+ * a min_eig_threshold that is not >= 0 (NaN included), n_points < 0, a null pointer with n_points > 0.
+ * n_points == 0: LH_OK.
+ */
+typedef struct lh_klt_input {
+    int32_t cols, rows;         /* level-0 image size (>= 12)                                         */
+    int64_t step;               /* bytes per image row (>= cols)                                      */
+    const uint8_t *img1;        /* [rows][step] previous / left image                                 */
+    const uint8_t *img2;        /* [rows][step] current / right image                                 */
+    int32_t n_points;
+    const float *kp1;           /* [n_points][2] keypoints in img1                                    */
+    int32_t has_initial;        /* kp2 on entry is the guess (OPTFLOW_USE_INITIAL_FLOW)               */
+    int32_t max_level;          /* 0..3; the reference: 3                                             */
+    int32_t max_iters;          /* >= 1; the reference: 30                                            */
+    double epsilon;             /* > 0; the reference: 0.01                                           */
+    double min_eig_threshold;   /* >= 0; the reference: 1e-4 (OpenCV's default)                       */
+} lh_klt_input;
+int lh_klt_track(lh_handle *h, const lh_klt_input *in, lh_lk_result *out);
+
+/*
+ * lh_stereo_landmarks with this tracker: lh_klt_track from the left image (klt.img1, klt.kp1) to the right (klt.img2),
+ * then lh_triangulate on every tracked pair where the tracker left them on the device.  kp2 and success are bitwise
+ * lh_klt_track's; pt and flags are bitwise lh_triangulate's on them; a failed track carries flag bit 4 alone.
+ */
+typedef struct lh_klt_stereo_input {
+    lh_klt_input klt;           /* img1 = left, img2 = right */
+    const double *pose_Tcw;     /* as lh_stereo_input's, from here on */
+    const double *cam_K;
+    double sing_ratio_thr;
+    int32_t gate;
+    double y_max, z_min, z_max;
+    const double *T_out;
+} lh_klt_stereo_input;
+int lh_klt_stereo_landmarks(lh_handle *h, const lh_klt_stereo_input *in, lh_stereo_result *out);
 
 /*
  * Shi-Tomasi corner detection, replacing Frontend::DetectFeatures (src/frontend_lego.cpp:292-310): a mask with a

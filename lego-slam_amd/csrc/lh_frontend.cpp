@@ -1,5 +1,6 @@
 // lh_frontend.cpp — the frontend entry points of the C ABI (include/lego_ba.h) on the solver's handle and stream:
-// lh_estimate_pose, lh_lk_track, lh_triangulate, lh_stereo_landmarks, lh_detect_features.  Each checks its arguments,
+// lh_estimate_pose, lh_lk_track, lh_klt_track, lh_triangulate, lh_stereo_landmarks, lh_klt_stereo_landmarks,
+// lh_detect_features.  Each checks its arguments,
 // grows its buffers (lh_handle.h FrontendState), enqueues copies and kernels, synchronises and copies out.
 #include <cmath>
 
@@ -306,14 +307,11 @@ int triangulate_impl(lh_handle* h, const lh_tri_input* in, lh_tri_result* out) {
     return LH_OK;
 }
 
-// lh_lk_track left -> right, then k_triangulate on kp1 / kp2 / success where the tracker left them
-int stereo_landmarks_impl(lh_handle* h, const lh_stereo_input* in, lh_stereo_result* out) {
-    if (!h || !in || !out) return LH_E_BADARG;
-    const int n = in->lk.n_points;
-    if (!in->pose_Tcw || (n > 0 && (!out->pt || !out->flags))) return LH_E_BADARG;
-    out->n_accepted = 0;
-    FrontendCall call(h);
-    STAGE(lk_enqueue(call, &in->lk, out->kp2, out->success));
+// a tracker's launches (lk_enqueue or klt_enqueue) left -> right are enqueued: k_triangulate on kp1 / kp2 / success where
+// the tracker left them, then one download.  In: lh_stereo_input or lh_klt_stereo_input (one set of field names)
+template <typename In>
+int stereo_finish(FrontendCall& call, int n, const In* in, lh_stereo_result* out) {
+    lh_handle* h = call.h;
     hipStream_t s = call.s;
     HIPCHK(h->fe.t_in.ensure(sizeof(double) * (12 + 4) * 2));
     lh_tri_args a{};
@@ -335,6 +333,108 @@ int stereo_landmarks_impl(lh_handle* h, const lh_stereo_input* in, lh_stereo_res
     STAGE(call.time(&out->time_ms));
     out->n_accepted = tri_count_accepted(out->flags, n);
     return LH_OK;
+}
+
+// lh_lk_track left -> right, then the triangulation
+int stereo_landmarks_impl(lh_handle* h, const lh_stereo_input* in, lh_stereo_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    const int n = in->lk.n_points;
+    if (!in->pose_Tcw || (n > 0 && (!out->pt || !out->flags))) return LH_E_BADARG;
+    out->n_accepted = 0;
+    FrontendCall call(h);
+    STAGE(lk_enqueue(call, &in->lk, out->kp2, out->success));
+    return stereo_finish(call, n, in, out);
+}
+
+// cv::calcOpticalFlowPyrLK as lh_klt.h defines it (include/lego_ba.h).  klt_check: the argument
+// errors.  klt_enqueue (n_points > 0): upload both images and the keypoints into the tracker's buffers (lh_lk_track's:
+// a handle runs one tracker at a time), build the pyramids (k_klt_pyr per level and image, levels 1.. packed), track
+// (k_klt_track); it starts the call's timing in front of the first kernel.  kp2 (host): the guess when in->has_initial.
+int klt_check(const lh_klt_input* in, const float* kp2, const uint8_t* success) {
+    if (in->cols < LH_KLT_MIN_SIZE || in->rows < LH_KLT_MIN_SIZE || in->step < in->cols || in->n_points < 0) return LH_E_BADARG;
+    if (in->max_level < 0 || in->max_level > LH_KLT_MAX_LEVELS - 1 || in->max_iters < 1) return LH_E_BADARG;
+    if (!(in->epsilon > 0.0) || !(in->min_eig_threshold >= 0.0)) return LH_E_BADARG;
+    if (in->n_points > 0 && (!in->img1 || !in->img2 || !in->kp1 || !kp2 || !success)) return LH_E_BADARG;
+    return LH_OK;
+}
+
+int klt_enqueue(FrontendCall& call, const lh_klt_input* in, const float* kp2) {
+    const int n = in->n_points;
+    STAGE(call.select());
+    lh_klt_args a{};
+    a.n_levels = lh_klt_level_sizes(in->cols, in->rows, in->max_level, a.I.cols, a.I.rows);
+    int64_t off[LH_KLT_MAX_LEVELS];
+    off[0] = 0;
+    a.I.step[0] = in->step;
+    int64_t total = (int64_t)in->rows * in->step;
+    for (int l = 1; l < a.n_levels; ++l) {
+        a.I.step[l] = a.I.cols[l];
+        off[l] = total;
+        total += (int64_t)a.I.cols[l] * a.I.rows[l];
+    }
+    hipStream_t s = call.s;
+    FrontendState& fe = call.h->fe;
+    HIPCHK(fe.k_img[0].ensure((size_t)total));
+    HIPCHK(fe.k_img[1].ensure((size_t)total));
+    HIPCHK(fe.k_kp1.ensure(2 * (size_t)n));
+    HIPCHK(fe.k_kp2.ensure(2 * (size_t)n));
+    HIPCHK(fe.k_succ.ensure((size_t)n));
+    // as lk_enqueue: the caller's last row guarantees only `cols` readable bytes.  No tap reads a row's padding (every
+    // read is at a REFLECT_101 index inside [0, cols)), so the last row's tail stays as the buffer has it
+    const size_t img_bytes = (size_t)(in->rows - 1) * (size_t)in->step + (size_t)in->cols;
+    for (int im = 0; im < 2; ++im)
+        HIPCHK(hipMemcpyAsync(fe.k_img[im].p, im ? in->img2 : in->img1, img_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(fe.k_kp1.p, in->kp1, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
+    if (in->has_initial) HIPCHK(hipMemcpyAsync(fe.k_kp2.p, kp2, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
+    a.J = a.I;
+    for (int l = 0; l < a.n_levels; ++l) {
+        a.I.data[l] = fe.k_img[0].p + off[l];
+        a.J.data[l] = fe.k_img[1].p + off[l];
+    }
+    a.n_points = n;
+    a.kp1 = fe.k_kp1.p;
+    a.kp2 = fe.k_kp2.p;
+    a.success = fe.k_succ.p;
+    a.has_initial = in->has_initial ? 1 : 0;
+    a.max_iters = in->max_iters;
+    a.eps2 = in->epsilon * in->epsilon;
+    a.min_eig = in->min_eig_threshold;
+    STAGE(call.start());
+    for (int l = 1; l < a.n_levels; ++l)
+        for (int im = 0; im < 2; ++im) {
+            const lh_klt_levels& v = im ? a.J : a.I;
+            HIPCHK(lh_launch_klt_pyr(s, v.data[l - 1], v.cols[l - 1], v.rows[l - 1], v.step[l - 1], fe.k_img[im].p + off[l],
+                                     v.cols[l], v.rows[l]));
+        }
+    HIPCHK(lh_launch_klt_track(s, &a));
+    return LH_OK;
+}
+
+int klt_track_impl(lh_handle* h, const lh_klt_input* in, lh_lk_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    STAGE(klt_check(in, out->kp2, out->success));
+    out->time_ms = 0.0;
+    if (in->n_points == 0) return LH_OK;
+    FrontendCall call(h);
+    STAGE(klt_enqueue(call, in, out->kp2));
+    STAGE(call.stop());
+    STAGE(lk_download(call, in->n_points, out->kp2, out->success));
+    HIPCHK(hipStreamSynchronize(call.s));
+    return call.time(&out->time_ms);
+}
+
+// lh_klt_track left -> right, then the triangulation
+int klt_stereo_landmarks_impl(lh_handle* h, const lh_klt_stereo_input* in, lh_stereo_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    const int n = in->klt.n_points;
+    STAGE(klt_check(&in->klt, out->kp2, out->success));
+    if (!in->pose_Tcw || (n > 0 && (!out->pt || !out->flags))) return LH_E_BADARG;
+    out->n_accepted = 0;
+    out->time_ms = 0.0;
+    if (n == 0) return LH_OK;
+    FrontendCall call(h);
+    STAGE(klt_enqueue(call, &in->klt, out->kp2));
+    return stereo_finish(call, n, in, out);
 }
 
 // Frontend::DetectFeatures (frontend_lego.cpp:292-310): the mask's exclusion boxes, then cv::GFTTDetector's
@@ -441,6 +541,10 @@ int lh_stereo_landmarks(lh_handle* h, const lh_stereo_input* in, lh_stereo_resul
 }
 int lh_detect_features(lh_handle* h, const lh_detect_input* in, lh_detect_result* out) {
     return no_throw(detect_features_impl, h, in, out);
+}
+int lh_klt_track(lh_handle* h, const lh_klt_input* in, lh_lk_result* out) { return no_throw(klt_track_impl, h, in, out); }
+int lh_klt_stereo_landmarks(lh_handle* h, const lh_klt_stereo_input* in, lh_stereo_result* out) {
+    return no_throw(klt_stereo_landmarks_impl, h, in, out);
 }
 
 }  // extern "C"

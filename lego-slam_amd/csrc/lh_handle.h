@@ -70,7 +70,7 @@ struct FrontendState {
     DevBuf<uint8_t> f_in, f_out;
     DevBuf<double> f_res;
     HostBuf<uint8_t> s_fin, s_fout;
-    // LK optical flow (lh_lk_track): both images' pyramids, keypoints
+    // optical flow (lh_lk_track, lh_klt_track; the stereo calls read them in place): both images' pyramids, keypoints
     DevBuf<uint8_t> k_img[2], k_succ;
     DevBuf<float> k_kp1, k_kp2;
     // triangulation (lh_triangulate, lh_stereo_landmarks): the inputs packed into one arena, the outputs into another

@@ -1,12 +1,13 @@
 // lh_launch.h — the one declaration of every kernel launcher.  The definitions (lh_lin.hip, lh_kernels.hip and its lh_probe.hip, lh_frames.hip,
-// lh_aux.hip, lh_lk.hip, lh_tri.hip, lh_gftt.hip) and the callers (lh_host.cpp, lh_frontend.cpp) all include it: the symbols are extern "C", so only
+// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip) and the callers (lh_host.cpp, lh_frontend.cpp) all include it: the symbols are extern "C", so only
 // the compiler, seeing a definition beside this declaration, can tell that the two sides disagree.
-// (lh_tri.h and lh_gftt.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.)
+// (lh_tri.h, lh_gftt.h and lh_klt.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "lh_common.h"
 #include "lh_gftt.h"
+#include "lh_klt.h"
 #include "lh_lk.h"
 #include "lh_tri.h"
 
@@ -55,6 +56,9 @@ hipError_t lh_launch_lk_pyr(hipStream_t st, const uint8_t* src, int sw, int sh, 
 hipError_t lh_launch_lk_track(hipStream_t st, const lh_lk_levels* L1, const lh_lk_levels* L2, int levels, int n,
                               const float* kp1, const float* kp2_in, float* kp2_out, uint8_t* success, int inverse,
                               int has_initial);
+hipError_t lh_launch_klt_pyr(hipStream_t st, const uint8_t* src, int sw, int sh, int64_t sstep, uint8_t* dst, int dw,
+                             int dh);
+hipError_t lh_launch_klt_track(hipStream_t st, const lh_klt_args* a);
 hipError_t lh_launch_triangulate(hipStream_t st, const lh_tri_args* a);
 hipError_t lh_launch_gftt_front(hipStream_t st, const lh_gftt_args* a);
 hipError_t lh_launch_gftt_rounds(hipStream_t st, const lh_gftt_args* a, int first, int count);

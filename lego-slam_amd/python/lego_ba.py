@@ -221,6 +221,18 @@ class LhStereoResult(C.Structure):
                 ("n_accepted", C.c_int32), ("time_ms", C.c_double)]
 
 
+class LhKltInput(C.Structure):
+    _fields_ = [
+        ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int64), ("img1", C.c_void_p), ("img2", C.c_void_p),
+        ("n_points", C.c_int32), ("kp1", C.c_void_p), ("has_initial", C.c_int32), ("max_level", C.c_int32),
+        ("max_iters", C.c_int32), ("epsilon", C.c_double), ("min_eig_threshold", C.c_double),
+    ]
+
+
+class LhKltStereoInput(C.Structure):
+    _fields_ = [("klt", LhKltInput)] + LhStereoInput._fields_[1:]
+
+
 class LhDetectInput(C.Structure):
     _fields_ = [
         ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int64), ("img", C.c_void_p), ("mask", C.c_void_p),
@@ -249,6 +261,7 @@ ABI_SYMBOLS = [
     "lh_create", "lh_destroy", "lh_solve", "lh_upload", "lh_solve_resident",
     "lh_kernel_stats_get", "lh_kernel_stats_reset", "lh_classify_outliers", "lh_set_profiling",
     "lh_estimate_pose", "lh_lk_track", "lh_triangulate", "lh_stereo_landmarks", "lh_detect_features",
+    "lh_klt_track", "lh_klt_stereo_landmarks",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
     "lh_debug_batch",
@@ -286,6 +299,9 @@ def ba_lib():
             lib.lh_stereo_landmarks.argtypes = [C.c_void_p, C.POINTER(LhStereoInput), C.POINTER(LhStereoResult)]
         if hasattr(lib, "lh_detect_features"):
             lib.lh_detect_features.argtypes = [C.c_void_p, C.POINTER(LhDetectInput), C.POINTER(LhDetectResult)]
+        if hasattr(lib, "lh_klt_track"):
+            lib.lh_klt_track.argtypes = [C.c_void_p, C.POINTER(LhKltInput), C.POINTER(LhLkResult)]
+            lib.lh_klt_stereo_landmarks.argtypes = [C.c_void_p, C.POINTER(LhKltStereoInput), C.POINTER(LhStereoResult)]
         lib.lh_classify_outliers.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lh_debug_event_floor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -563,6 +579,60 @@ class Solver:
         r = LhStereoResult()
         r.kp2, r.success, r.pt, r.flags = _ptr(k2), _ptr(ok), _ptr(out["pt"]), _ptr(out["flags"])
         _check(ba_lib().lh_stereo_landmarks(self.h, C.byref(s), C.byref(r)), "lh_stereo_landmarks")
+        out["success"] = ok.astype(bool)
+        out["n_accepted"], out["time_ms"] = r.n_accepted, r.time_ms
+        return out
+
+    @staticmethod
+    def _klt_input(img1, img2, kp1, kp2_init, max_level, max_iters, epsilon, min_eig):
+        """An LhKltInput on 8-bit images (2-D uint8, rows of one stride >= cols taken as they are), the arrays it
+        points to, and the kp2 / success buffers."""
+        def rows_ok(a):
+            return a.ndim == 2 and a.dtype == np.uint8 and a.strides[1] == 1 and a.strides[0] >= a.shape[1]
+        i1, i2 = np.asarray(img1), np.asarray(img2)
+        if not (rows_ok(i1) and rows_ok(i2) and i1.strides == i2.strides):
+            i1, i2 = np.ascontiguousarray(img1, dtype=np.uint8), np.ascontiguousarray(img2, dtype=np.uint8)
+        if i1.shape != i2.shape or i1.ndim != 2:
+            raise ValueError("images must be 2-D uint8 arrays of one shape")
+        k1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
+        n = k1.shape[0]
+        k2 = (np.zeros((n, 2), np.float32) if kp2_init is None
+              else np.array(kp2_init, dtype=np.float32, copy=True).reshape(-1, 2))
+        ok = np.zeros(n, np.uint8)
+        a = LhKltInput()
+        a.rows, a.cols = i1.shape
+        a.step = i1.strides[0]
+        a.img1, a.img2 = _ptr(i1), _ptr(i2)
+        a.n_points, a.kp1 = n, _ptr(k1)
+        a.has_initial, a.max_level, a.max_iters = int(kp2_init is not None), int(max_level), int(max_iters)
+        a.epsilon, a.min_eig_threshold = float(epsilon), float(min_eig)
+        return a, (i1, i2, k1), k2, ok
+
+    def klt_track(self, img1, img2, kp1, kp2_init=None, max_level=3, max_iters=30, epsilon=0.01, min_eig=1e-4):
+        """cv::calcOpticalFlowPyrLK with an 11 x 11 window as include/lego_ba.h defines it (the reference's live
+        trackers, frontend_lego.cpp:383-463; the defaults are its parameters) through lh_klt_track.  kp2_init: the
+        guess (OPTFLOW_USE_INITIAL_FLOW).  Returns kp2 [n, 2] float32, success [n] bool and the device time."""
+        a, _keep, k2, ok = self._klt_input(img1, img2, kp1, kp2_init, max_level, max_iters, epsilon, min_eig)
+        r = LhLkResult()
+        r.kp2, r.success = _ptr(k2), _ptr(ok)
+        _check(ba_lib().lh_klt_track(self.h, C.byref(a), C.byref(r)), "lh_klt_track")
+        return dict(kp2=k2, success=ok.astype(bool), time_ms=r.time_ms)
+
+    def klt_stereo_landmarks(self, img_left, img_right, kp_left, poses, K=None, kp_right_init=None, max_level=3,
+                             max_iters=30, epsilon=0.01, min_eig=1e-4, thr=1e-3, gate=None, T_out=None):
+        """stereo_landmarks with klt_track as the tracker (lh_klt_stereo_landmarks); the same result dict."""
+        s = LhKltStereoInput()
+        s.klt, _keep_klt, k2, ok = self._klt_input(img_left, img_right, kp_left, kp_right_init, max_level, max_iters,
+                                                   epsilon, min_eig)
+        n = s.klt.n_points
+        keep = dict(pose=np.ascontiguousarray(poses, np.float64).reshape(2, 12),
+                    K=None if K is None else np.ascontiguousarray(K, np.float64).reshape(2, 4))
+        s.pose_Tcw, s.cam_K = _ptr(keep["pose"]), _ptr(keep["K"])
+        self._tri_common(s, keep, thr, gate, T_out)
+        out = dict(kp2=k2, pt=np.zeros((n, 3)), flags=np.zeros(n, np.uint8))
+        r = LhStereoResult()
+        r.kp2, r.success, r.pt, r.flags = _ptr(k2), _ptr(ok), _ptr(out["pt"]), _ptr(out["flags"])
+        _check(ba_lib().lh_klt_stereo_landmarks(self.h, C.byref(s), C.byref(r)), "lh_klt_stereo_landmarks")
         out["success"] = ok.astype(bool)
         out["n_accepted"], out["time_ms"] = r.n_accepted, r.time_ms
         return out
