@@ -549,6 +549,12 @@ int lh_debug_ladder(lh_handle *h, int *rungs, int *skipped);
    may be NULL) the acceptances among them: [0] re-run by the next chain as a full trial, [1] re-run and stopping
    the loop.  Solves that return arrays only (else -1). */
 int lh_debug_batch(lh_handle *h, int *batch_max, int *batches, int *retrials);
+/* the reduced pose system as the last chain left it, copied to out[cap] behind the handle's stream.  which: 0 the
+   staged packed system (k_reduce's output: npairs 6x6 blocks of S, b_s, b_p, diag H_pp, the chunk scalars), 1 the
+   committed one, 2 the pending pose step (6 n_poses doubles), 3 the staged half of k_reduce's image of S where the
+   controller reads S from one (k_ctrl's LDS layout, k_ctrl_b's band; *n_out 0 otherwise).  *n_out: the doubles the
+   buffer holds; *npairs_out: the blocks of S.  LH_E_BADARG without an uploaded window or with cap < *n_out. */
+int lh_debug_reduced_system(lh_handle *h, int which, double *out, int64_t cap, int64_t *n_out, int32_t *npairs_out);
 
 #ifdef __cplusplus
 }

@@ -202,7 +202,12 @@ __device__ __forceinline__ void wave_sum_desc(double (&v)[N]) {
 __device__ __forceinline__ double wave_max(double v) {
     v = fmax(v, dpp_d<0xB1>(v));                                            // ^1
     v = fmax(v, dpp_d<0x4E>(v));                                            // ^2
-    v = fmax(v, (__lane_id() & 4) ? dpp_d<0x124>(v) : dpp_d<0x12C>(v));     // ^4
+    {   // ^4: both rotations by every lane, then the select, as group_sum.  (A DPP in each arm of a conditional runs
+        // under that arm's exec mask, and its source lane, in the other arm, is then disabled and reads as 0: the
+        // step was a no-op, and max |diag H_ll| lost the landmarks whose lead lane has bit 2 set, lg <= 2.)
+        const double a = dpp_d<0x12C>(v), b = dpp_d<0x124>(v);
+        v = fmax(v, (__lane_id() & 4) ? b : a);
+    }
     v = fmax(v, dpp_d<0x128>(v));                                           // ^8
     const long long x = __double_as_longlong(v);
     auto lo = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);

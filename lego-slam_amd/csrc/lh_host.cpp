@@ -1484,6 +1484,35 @@ int lh_debug_controller(lh_handle* h, int* which) {
     return LH_OK;
 }
 
+// test hook: the reduced system as the last chain left it (which: include/lego_ba.h), read behind the handle's stream
+int lh_debug_reduced_system(lh_handle* h, int which, double* out, int64_t cap, int64_t* n_out, int32_t* npairs_out) {
+    if (!h || !out || !n_out || !npairs_out || which < 0 || which > 3) return LH_E_BADARG;
+    if (!h->uploaded) return LH_E_BADARG;
+    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const double* src = nullptr;
+    int64_t n = 0;
+    if (which == 0 || which == 1) {
+        src = which == 0 ? h->d_rs_stage.p : h->d_rs_commit.p;
+        n = h->LY.total;
+    } else if (which == 2) {   // the pending pose step: rung ctrl->lad of the ladder's steps
+        int32_t lad = 0;
+        HIPCHK(hipMemcpy(&lad, reinterpret_cast<const char*>(h->d_ctrl.p) + offsetof(lh_ctrl, lad), sizeof(lad),
+                         hipMemcpyDeviceToHost));
+        n = 6 * (int64_t)h->P;
+        if (lad < 0 || lad >= std::max(h->cfg.ladder, 1)) return LH_E_STATE;
+        src = h->d_dxp.p + (size_t)lad * (size_t)n;
+    } else {   // the staged half of k_reduce's image of S (prm.img, prm.bimg; nothing otherwise)
+        src = h->d_img.p;
+        n = (int64_t)(h->cfg.n_img / 2);
+    }
+    *n_out = n;
+    *npairs_out = h->LY.npairs;
+    if (cap < n) return LH_E_BADARG;
+    if (n > 0) HIPCHK(hipMemcpy(out, src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return LH_OK;
+}
+
 int lh_debug_mfma_probe(const double* A, const double* B, double* D) {
     if (lh_launch_mfma_probe(A, B, D) != hipSuccess) return LH_E_HIP;
     if (hipDeviceSynchronize() != hipSuccess) return LH_E_HIP;

@@ -264,7 +264,7 @@ ABI_SYMBOLS = [
     "lh_klt_track", "lh_klt_stereo_landmarks",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
-    "lh_debug_batch",
+    "lh_debug_batch", "lh_debug_reduced_system",
 ]
 
 _balib = None
@@ -312,6 +312,9 @@ def ba_lib():
         lib.lh_debug_ladder.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         if hasattr(lib, "lh_debug_batch"):   # (an older library of an A/B run lacks it)
             lib.lh_debug_batch.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if hasattr(lib, "lh_debug_reduced_system"):
+            lib.lh_debug_reduced_system.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                                    C.POINTER(C.c_int32)]
         _balib = lib
     return _balib
 
@@ -768,6 +771,21 @@ class Solver:
         m, k, rt = C.c_int(0), C.c_int(0), (C.c_int * 2)()
         _check(ba_lib().lh_debug_batch(self.h, C.byref(m), C.byref(k), rt), "lh_debug_batch")
         return m.value, k.value, (rt[0], rt[1])
+
+    def reduced_system(self, which=0):
+        """The reduced system as the last chain left it (lh_debug_reduced_system): (the raw vector, npairs).
+        which 0: the staged packed system (lh_rs_make's layout), 1: the committed one, 2: the pending pose step,
+        3: the staged half of k_reduce's image of S (empty where the controller reads the packed blocks)."""
+        n, npairs = C.c_int64(0), C.c_int32(0)
+        probe = np.zeros(1)
+        st = ba_lib().lh_debug_reduced_system(self.h, int(which), _ptr(probe), 0, C.byref(n), C.byref(npairs))
+        if st != LH_OK and not (st == LH_E_BADARG and n.value > 0):
+            raise LhError(st, "lh_debug_reduced_system")
+        out = np.zeros(n.value)
+        if n.value:
+            _check(ba_lib().lh_debug_reduced_system(self.h, int(which), _ptr(out), n.value, C.byref(n),
+                                                    C.byref(npairs)), "lh_debug_reduced_system")
+        return out, npairs.value
 
     def comm_count(self):
         """Reduced-system all-reduces the last solve issued (lh_debug_comm_count)."""
