@@ -22,6 +22,7 @@
  *     Frontend::EstimateCurrentPose frontend_lego.cpp:157-250 lh_estimate_pose (batched)
  *     LKOpticalFlow4Layer / 1Layer  algorithm.cpp:11-206      lh_lk_track
  *     cv::calcOpticalFlowPyrLK      frontend_lego.cpp:383-463 lh_klt_track, lh_klt_stereo_landmarks (the live trackers)
+ *     Frontend::Track               frontend_lego.cpp:48-75   lh_track_frame (guesses, KLT, selection, pose: one call per frame)
  *     triangulation                 algorithm.h:11-34         lh_triangulate (batched)
  *     Frontend::TriangulateNewPoints frontend_lego.cpp:111-155 lh_stereo_landmarks (LK left -> right + triangulation,
  *     Frontend::BuildInitMap        frontend_lego.cpp:323-362                       one call per stereo frame)
@@ -507,6 +508,65 @@ typedef struct lh_detect_result {
                                    included; copies of the inputs and outputs excluded) */
 } lh_detect_result;
 int lh_detect_features(lh_handle *h, const lh_detect_input *in, lh_detect_result *out);
+
+/*
+ * One frame of Frontend::Track (src/frontend_lego.cpp:48-75) without a host step in between: the tracker's guesses
+ * (TrackLastFrameLKOpticalFlowOpenCV, :383-398), lh_klt_track last-left -> current-left (:402-406), the tracked features
+ * that carry a map point (:408-417), and lh_estimate_pose on them (EstimateCurrentPose, :157-258).  One upload besides
+ * the image(s), one download, one synchronise.
+ *
+ *   guess    feature i with has_point, X = pts_w[i], T = pose_Tcw, E = cam_ext, every operation one correctly rounded
+ *            binary64 operation and none contracted into an FMA:
+ *              Pb_r = ((T[r][0] X0 + T[r][1] X1) + T[r][2] X2) + T[r][3]          r = 0..2
+ *              Pc_r = ((E[r][0] Pb0 + E[r][1] Pb1) + E[r][2] Pb2) + E[r][3]       (world2camera, src/camera.cpp:8-14)
+ *              u = (fx Pc0) / Pc2 + cx,  v = (fy Pc1) / Pc2 + cy                    (camera2pixel, camera.cpp:16-19)
+ *            and the guess is ((float)u, (float)v), round to nearest even, a value past FLT_MAX +-inf.  Without
+ *            has_point the guess is kp1[i] (:395-396).  A NaN or infinite guess is no special case: lh_klt_track gives
+ *            it success 0.  The reference forms pose_ * T_c_w first, as a Sophus quaternion product; the two orders
+ *            agree to rounding before the conversion to float.  Parity with Sophus to the bit is unverified, like every
+ *            other Sophus / OpenCV statement in this header.
+ *   track    lh_klt_track on (img1, img2, kp1) with those guesses (has_initial) and klt's parameters: kp2 and success
+ *            are bitwise the values it would return.
+ *   select   the edges are the features with success[i] && has_point[i], in ascending i: the order features_left_ gets
+ *            (:409-416) and EstimateCurrentPose walks it in (:179-197).  An edge has the point pts_w[i], the measurement
+ *            ((double)kp2[i].x, (double)kp2[i].y) (toVec2) and the entry flag 0.
+ *   pose     lh_estimate_pose on that one frame from pose_Tcw, with K and the handle's options: pose_Tcw, the edges'
+ *            flags and chi2, n_inliers and iterations are bitwise its outputs.  With no edge Problem::solve returns
+ *            false: out->pose_Tcw is the input bit for bit and n_inliers = iterations = 0.
+ *
+ * The resident image.  The call keeps img2 and its pyramid in buffers of its own, which no other entry point reads or
+ * writes.  klt.img1 == NULL means the img2 of the previous successful lh_track_frame on this handle: LH_E_STATE if
+ * there is none, or if its cols / rows differ from this call's.  An argument error leaves the resident image as it
+ * was; a call that fails after it began to enqueue invalidates it.  n_points == 0 is LH_OK with pose_Tcw copied
+ * through and the counts 0; img1 is then not looked at, and a non-NULL img2 still becomes resident (uploaded, its
+ * pyramid built): the priming call after StereoInit.
+ *
+ * LH_E_BADARG: lh_klt_track's argument errors (on img2, and on img1 when given), a null pts_w when some feature can
+ * have a point, a null kp2 or success with n_points > 0.
+ */
+typedef struct lh_track_input {
+    lh_klt_input klt;         /* img1 = last_frame_->left_img_ (NULL: the resident image), img2 = current_frame_->left_img_,
+                                 kp1 = the last frame's features_left_; klt.has_initial is not read (the guesses are made
+                                 here); klt.step describes img2, and img1 when given */
+    const double *pts_w;      /* [n_points][3] mp->pos_ of each feature; read only where has_point */
+    const uint8_t *has_point; /* [n_points] nonzero: kp->map_point_.lock(); NULL: every feature has one */
+    double pose_Tcw[12];      /* current_frame_->Pose() on entry: relative_motion_ * last_frame_->Pose() (:50) */
+    double cam_ext[12];       /* camera_left_->pose(), row-major [R|t] */
+    double K[4];              /* fx, fy, cx, cy */
+} lh_track_input;
+typedef struct lh_track_result {
+    float *kp2;               /* [n_points][2] tracked positions (required when n_points > 0) */
+    uint8_t *success;         /* [n_points]     (required when n_points > 0) */
+    double pose_Tcw[12];      /* the pose after EstimateCurrentPose's round four */
+    uint8_t *is_outlier;      /* [n_points] or NULL: the feature's flag after round four; 0 for a feature that was no edge */
+    double *edge_chi2;        /* [n_points] or NULL: lh_frames_result.edge_chi2 of the feature's edge; 0.0 for no edge */
+    int32_t n_tracked;        /* num_good_pts (:408-417) */
+    int32_t n_edges;          /* features.size() in EstimateCurrentPose */
+    int32_t n_inliers;        /* its return value (tracking_inliers_) */
+    int32_t iterations;       /* LM iterations over the four rounds */
+    double time_ms;           /* HIP-event bracket, first kernel to last, copies excluded */
+} lh_track_result;
+int lh_track_frame(lh_handle *h, const lh_track_input *in, lh_track_result *out);
 
 /* ---- test hooks (not part of the reference interface) ---- */
 /* f64 MFMA accumulator-layout probe: D(16x16) = A(16x4) * B(4x16), device pointers, row-major */

@@ -1,6 +1,6 @@
 // lh_frontend.cpp — the frontend entry points of the C ABI (include/lego_ba.h) on the solver's handle and stream:
 // lh_estimate_pose, lh_lk_track, lh_klt_track, lh_triangulate, lh_stereo_landmarks, lh_klt_stereo_landmarks,
-// lh_detect_features.  Each checks its arguments,
+// lh_detect_features, lh_track_frame.  Each checks its arguments,
 // grows its buffers (lh_handle.h FrontendState), enqueues copies and kernels, synchronises and copies out.
 #include <cmath>
 
@@ -46,6 +46,31 @@ int no_throw(int (*impl)(lh_handle*, const In*, Out*), lh_handle* h, const In* i
     }
 }
 
+// an 8-bit image to the device with its rows packed to `cols` bytes: only `cols` bytes of a caller's row are readable
+// (a cv::Mat ROI has step > cols)
+hipError_t upload_rows(hipStream_t s, uint8_t* dst, const uint8_t* src, int cols, int rows, int64_t step) {
+    if (step == cols) return hipMemcpyAsync(dst, src, (size_t)rows * (size_t)cols, hipMemcpyHostToDevice, s);
+    return hipMemcpy2DAsync(dst, (size_t)cols, src, (size_t)step, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice, s);
+}
+
+// lh_params of the handle's options with a frame's intrinsics (k_frames)
+lh_params frames_params(const lh_handle* h, const double* K) {
+    lh_params prm{};
+    prm.max_iters = h->opt.max_iters;
+    prm.max_trials = h->opt.max_trials;
+    prm.strategy = h->opt.strategy;
+    prm.lambda_given = h->opt.lambda_init >= 0.0;
+    prm.gate_mode = h->opt.gate_mode;
+    prm.precision = h->opt.precision;
+    prm.huber_delta = h->opt.huber_delta;
+    prm.stop_dchi2 = h->opt.stop_dchi2;
+    prm.tau = h->opt.tau;
+    prm.lambda_cap = h->opt.lambda_cap;
+    prm.lambda_init = h->opt.lambda_init;
+    for (int i = 0; i < 4; ++i) prm.K[i] = K[i];
+    return prm;
+}
+
 // Frontend::EstimateCurrentPose for a batch of frames (frontend_lego.cpp:157-250): upload, one
 // k_frames launch (one workgroup per frame), download.
 int estimate_pose_impl(lh_handle* h, const lh_frames* in, lh_frames_result* out) {
@@ -89,19 +114,7 @@ int estimate_pose_impl(lh_handle* h, const lh_frames* in, lh_frames_result* out)
     }
     HIPCHK(hipMemcpyAsync(fe.f_in.p, fe.s_fin.p, i_end, hipMemcpyHostToDevice, s));
     uint8_t *fi = fe.f_in.p, *fo = fe.f_out.p;
-    lh_params prm{};
-    prm.max_iters = h->opt.max_iters;
-    prm.max_trials = h->opt.max_trials;
-    prm.strategy = h->opt.strategy;
-    prm.lambda_given = h->opt.lambda_init >= 0.0;
-    prm.gate_mode = h->opt.gate_mode;
-    prm.precision = h->opt.precision;
-    prm.huber_delta = h->opt.huber_delta;
-    prm.stop_dchi2 = h->opt.stop_dchi2;
-    prm.tau = h->opt.tau;
-    prm.lambda_cap = h->opt.lambda_cap;
-    prm.lambda_init = h->opt.lambda_init;
-    for (int i = 0; i < 4; ++i) prm.K[i] = in->K[i];
+    const lh_params prm = frames_params(h, in->K);
     STAGE(call.start());
     HIPCHK(lh_launch_frames(s, F, (const int64_t*)(fi + i_ptr), (const double*)(fi + i_pose),
                             (const double*)(fi + i_pts), (const double*)(fi + i_uv), has_flag ? fi + i_flag : nullptr,
@@ -358,20 +371,39 @@ int klt_check(const lh_klt_input* in, const float* kp2, const uint8_t* success) 
     return LH_OK;
 }
 
+// One image's pyramid in a buffer: level 0 with rows `step` bytes apart, levels 1 .. n_levels - 1 packed behind it.
+// Fills v's step and (with a buffer) data from its cols and rows; returns the bytes.
+int64_t klt_pyramid_layout(lh_klt_levels* v, int n_levels, uint8_t* buf, int64_t step) {
+    int64_t total = (int64_t)v->rows[0] * step;
+    v->step[0] = step;
+    v->data[0] = buf;
+    for (int l = 1; l < n_levels; ++l) {
+        v->step[l] = v->cols[l];
+        v->data[l] = buf ? buf + total : nullptr;
+        total += (int64_t)v->cols[l] * v->rows[l];
+    }
+    return total;
+}
+
+// The tracker's kernels on images, keypoints and guesses that are on the device (a: both pyramids laid out): the levels
+// first_I .. of I and 1 .. of J (k_klt_pyr, level by level, I before J), then k_klt_track.
+int klt_pyr_track(hipStream_t s, const lh_klt_args& a, int first_I) {
+    for (int l = 1; l < a.n_levels; ++l)
+        for (int im = l < first_I ? 1 : 0; im < 2; ++im) {
+            const lh_klt_levels& v = im ? a.J : a.I;
+            HIPCHK(lh_launch_klt_pyr(s, v.data[l - 1], v.cols[l - 1], v.rows[l - 1], v.step[l - 1], const_cast<uint8_t*>(v.data[l]),
+                                     v.cols[l], v.rows[l]));
+        }
+    HIPCHK(lh_launch_klt_track(s, &a));
+    return LH_OK;
+}
+
 int klt_enqueue(FrontendCall& call, const lh_klt_input* in, const float* kp2) {
     const int n = in->n_points;
     STAGE(call.select());
     lh_klt_args a{};
     a.n_levels = lh_klt_level_sizes(in->cols, in->rows, in->max_level, a.I.cols, a.I.rows);
-    int64_t off[LH_KLT_MAX_LEVELS];
-    off[0] = 0;
-    a.I.step[0] = in->step;
-    int64_t total = (int64_t)in->rows * in->step;
-    for (int l = 1; l < a.n_levels; ++l) {
-        a.I.step[l] = a.I.cols[l];
-        off[l] = total;
-        total += (int64_t)a.I.cols[l] * a.I.rows[l];
-    }
+    const int64_t total = klt_pyramid_layout(&a.I, a.n_levels, nullptr, in->step);
     hipStream_t s = call.s;
     FrontendState& fe = call.h->fe;
     HIPCHK(fe.k_img[0].ensure((size_t)total));
@@ -387,10 +419,8 @@ int klt_enqueue(FrontendCall& call, const lh_klt_input* in, const float* kp2) {
     HIPCHK(hipMemcpyAsync(fe.k_kp1.p, in->kp1, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
     if (in->has_initial) HIPCHK(hipMemcpyAsync(fe.k_kp2.p, kp2, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
     a.J = a.I;
-    for (int l = 0; l < a.n_levels; ++l) {
-        a.I.data[l] = fe.k_img[0].p + off[l];
-        a.J.data[l] = fe.k_img[1].p + off[l];
-    }
+    klt_pyramid_layout(&a.I, a.n_levels, fe.k_img[0].p, in->step);
+    klt_pyramid_layout(&a.J, a.n_levels, fe.k_img[1].p, in->step);
     a.n_points = n;
     a.kp1 = fe.k_kp1.p;
     a.kp2 = fe.k_kp2.p;
@@ -400,14 +430,7 @@ int klt_enqueue(FrontendCall& call, const lh_klt_input* in, const float* kp2) {
     a.eps2 = in->epsilon * in->epsilon;
     a.min_eig = in->min_eig_threshold;
     STAGE(call.start());
-    for (int l = 1; l < a.n_levels; ++l)
-        for (int im = 0; im < 2; ++im) {
-            const lh_klt_levels& v = im ? a.J : a.I;
-            HIPCHK(lh_launch_klt_pyr(s, v.data[l - 1], v.cols[l - 1], v.rows[l - 1], v.step[l - 1], fe.k_img[im].p + off[l],
-                                     v.cols[l], v.rows[l]));
-        }
-    HIPCHK(lh_launch_klt_track(s, &a));
-    return LH_OK;
+    return klt_pyr_track(s, a, 1);
 }
 
 int klt_track_impl(lh_handle* h, const lh_klt_input* in, lh_lk_result* out) {
@@ -435,6 +458,150 @@ int klt_stereo_landmarks_impl(lh_handle* h, const lh_klt_stereo_input* in, lh_st
     FrontendCall call(h);
     STAGE(klt_enqueue(call, &in->klt, out->kp2));
     return stereo_finish(call, n, in, out);
+}
+
+// Frontend::Track (frontend_lego.cpp:48-75) in one call (include/lego_ba.h): upload img2 (and img1,
+// unless the resident image stands in for it) and one arena; k_track_guess, the tracker's kernels, k_track_pack and
+// k_frames behind one another on the device buffers; one download; one synchronise.  The edge count stays on the
+// device until then: k_frames reads it from the obs_ptr k_track_pack wrote.
+int track_frame_impl(lh_handle* h, const lh_track_input* in, lh_track_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    const lh_klt_input& k = in->klt;
+    const int n = k.n_points, cols = k.cols, rows = k.rows;
+    {
+        lh_klt_input chk = k;   // lh_klt_track's argument checks; a null img1 is the resident image
+        if (!chk.img1) chk.img1 = chk.img2;
+        STAGE(klt_check(&chk, out->kp2, out->success));
+    }
+    if (n > 0 && !in->pts_w) {
+        if (!in->has_point) return LH_E_BADARG;
+        for (int i = 0; i < n; ++i)
+            if (in->has_point[i]) return LH_E_BADARG;
+    }
+    FrontendState& fe = h->fe;
+    if (n > 0 && !k.img1 && !(fe.r_valid && fe.r_cols == cols && fe.r_rows == rows)) return LH_E_STATE;
+    for (int i = 0; i < 12; ++i) out->pose_Tcw[i] = in->pose_Tcw[i];
+    out->n_tracked = out->n_edges = out->n_inliers = out->iterations = 0;
+    out->time_ms = 0.0;
+    if (n == 0 && !k.img2) return LH_OK;
+    FrontendCall call(h);
+    STAGE(call.select());
+    hipStream_t s = call.s;
+    // from here on the resident image is in the making: valid again once the call has succeeded
+    const int slot_I = fe.r_cur, slot_J = 1 - fe.r_cur;
+    const int have_I = n == 0 ? LH_KLT_MAX_LEVELS : k.img1 ? 1 : fe.r_levels;   // I's first level to build (n == 0: no I)
+    fe.r_valid = false;
+    lh_klt_args a{};
+    {
+        lh_klt_levels full{};   // the buffers hold every level, whatever max_level a call asks for
+        const int n_full = lh_klt_level_sizes(cols, rows, LH_KLT_MAX_LEVELS - 1, full.cols, full.rows);
+        const size_t bytes = (size_t)klt_pyramid_layout(&full, n_full, nullptr, cols);
+        HIPCHK(fe.r_img[slot_J].ensure(bytes));
+        if (n > 0) HIPCHK(fe.r_img[slot_I].ensure(bytes));   // no change of a resident image: its size is this one
+    }
+    a.n_levels = lh_klt_level_sizes(cols, rows, k.max_level, a.I.cols, a.I.rows);
+    a.J = a.I;
+    klt_pyramid_layout(&a.I, a.n_levels, fe.r_img[slot_I].p, cols);
+    klt_pyramid_layout(&a.J, a.n_levels, fe.r_img[slot_J].p, cols);
+    // arena layouts (16-byte aligned segments)
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t N = (size_t)n;
+    const size_t i_pose = 0, i_pts = al(sizeof(double) * 12), i_kp1 = i_pts + al(sizeof(double) * 3 * N),
+                 i_hp = i_kp1 + al(sizeof(float) * 2 * N), i_end = i_hp + (in->has_point ? al(N) : 0);
+    const size_t o_pose = 0, o_cnt = al(sizeof(double) * 12), o_kp2 = o_cnt + al(sizeof(int32_t) * 4),
+                 o_succ = o_kp2 + al(sizeof(float) * 2 * N), o_idx = o_succ + al(N), o_flag = o_idx + al(sizeof(int32_t) * N),
+                 o_chi = o_flag + al(N), o_end = o_chi + al(sizeof(double) * N);
+    const size_t w_ptr = 0, w_pts = al(sizeof(int64_t) * 2), w_uv = w_pts + al(sizeof(double) * 3 * N),
+                 w_end = w_uv + al(sizeof(double) * 2 * N);
+    if (n > 0) {
+        HIPCHK(fe.tk_in.ensure(i_end));
+        HIPCHK(fe.tk_out.ensure(o_end));
+        HIPCHK(fe.tk_work.ensure(w_end));
+        HIPCHK(fe.f_res.ensure(2 * N));
+        HIPCHK(fe.s_tkin.ensure(i_end));
+        HIPCHK(fe.s_tkout.ensure(o_end));
+    }
+    HIPCHK(upload_rows(s, fe.r_img[slot_J].p, k.img2, cols, rows, k.step));
+    if (n > 0 && k.img1) HIPCHK(upload_rows(s, fe.r_img[slot_I].p, k.img1, cols, rows, k.step));
+    lh_track_args t{};
+    uint8_t *ti = fe.tk_in.p, *to = fe.tk_out.p, *tw = fe.tk_work.p;
+    if (n > 0) {
+        uint8_t* st = fe.s_tkin.p;
+        const ByteSeg seg[4] = {{st + i_pose, in->pose_Tcw, sizeof(double) * 12},
+                                {st + i_pts, in->pts_w, in->pts_w ? sizeof(double) * 3 * N : 0},
+                                {st + i_kp1, k.kp1, sizeof(float) * 2 * N},
+                                {st + i_hp, in->has_point, in->has_point ? N : 0}};
+        par_copy(h, seg, 4);
+        HIPCHK(hipMemcpyAsync(ti, st, i_end, hipMemcpyHostToDevice, s));
+        t.n_points = n;
+        t.kp1 = (const float*)(ti + i_kp1);
+        t.pts_w = (const double*)(ti + i_pts);
+        t.has_point = in->has_point ? ti + i_hp : nullptr;
+        for (int i = 0; i < 12; ++i) { t.pose[i] = in->pose_Tcw[i]; t.ext[i] = in->cam_ext[i]; }
+        for (int i = 0; i < 4; ++i) t.K[i] = in->K[i];
+        t.kp2 = (float*)(to + o_kp2);
+        t.success = to + o_succ;
+        t.obs_ptr = (int64_t*)(tw + w_ptr);
+        t.pts = (double*)(tw + w_pts);
+        t.uv = (double*)(tw + w_uv);
+        t.edge_feature = (int32_t*)(to + o_idx);
+        t.counts = (int32_t*)(to + o_cnt);
+        a.n_points = n;
+        a.kp1 = t.kp1;
+        a.kp2 = t.kp2;
+        a.success = to + o_succ;
+        a.has_initial = 1;
+        a.max_iters = k.max_iters;
+        a.eps2 = k.epsilon * k.epsilon;
+        a.min_eig = k.min_eig_threshold;
+    }
+    STAGE(call.start());
+    HIPCHK(lh_launch_track_guess(s, &t));
+    STAGE(klt_pyr_track(s, a, have_I));
+    if (n > 0) {
+        HIPCHK(lh_launch_track_pack(s, &t));
+        HIPCHK(lh_launch_frames(s, 1, t.obs_ptr, (const double*)(ti + i_pose), t.pts, t.uv, nullptr, frames_params(h, in->K),
+                                fe.f_res.p, (double*)(to + o_pose), to + o_flag, (double*)(to + o_chi), t.counts + 2,
+                                t.counts + 3));
+    }
+    STAGE(call.stop());
+    if (n > 0) {   // one download, up to the last output the caller asked for
+        const size_t want = out->edge_chi2 ? o_end : out->is_outlier ? o_chi : o_idx;
+        HIPCHK(hipMemcpyAsync(fe.s_tkout.p, to, want, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (n > 0) {
+        const uint8_t* st = fe.s_tkout.p;
+        const int32_t* cnt = (const int32_t*)(st + o_cnt);
+        const int32_t m = cnt[1];
+        if (m < 0 || m > n) return LH_E_HIP;
+        const ByteSeg seg[3] = {{out->pose_Tcw, st + o_pose, sizeof(double) * 12},
+                                {out->kp2, st + o_kp2, sizeof(float) * 2 * N},
+                                {out->success, st + o_succ, N}};
+        par_copy(h, seg, 3);
+        out->n_tracked = cnt[0];
+        out->n_edges = m;
+        out->iterations = cnt[2];
+        out->n_inliers = cnt[3];
+        // the edges' outputs back to their features
+        const int32_t* idx = (const int32_t*)(st + o_idx);
+        if (out->is_outlier) {
+            std::fill(out->is_outlier, out->is_outlier + n, (uint8_t)0);
+            for (int32_t e = 0; e < m; ++e) out->is_outlier[idx[e]] = st[o_flag + e];
+        }
+        if (out->edge_chi2) {
+            std::fill(out->edge_chi2, out->edge_chi2 + n, 0.0);
+            const double* chi = (const double*)(st + o_chi);
+            for (int32_t e = 0; e < m; ++e) out->edge_chi2[idx[e]] = chi[e];
+        }
+    }
+    STAGE(call.time(&out->time_ms));
+    fe.r_cur = slot_J;
+    fe.r_cols = cols;
+    fe.r_rows = rows;
+    fe.r_levels = a.n_levels;
+    fe.r_valid = true;
+    return LH_OK;
 }
 
 // Frontend::DetectFeatures (frontend_lego.cpp:292-310): the mask's exclusion boxes, then cv::GFTTDetector's
@@ -471,14 +638,9 @@ int detect_features_impl(lh_handle* h, const lh_detect_input* in, lh_detect_resu
     HIPCHK(fe.g_resp.ensure((size_t)std::max(limit, 1)));
     HIPCHK(fe.g_ctl.ensure(1));
     HIPCHK(fe.s_gctl.ensure(1));
-    // rows packed to `cols` bytes: only `cols` bytes of a caller's row are readable (a cv::Mat ROI has step > cols)
-    auto upload_rows = [&](uint8_t* dst, const uint8_t* src, int64_t step) {
-        if (step == cols) return hipMemcpyAsync(dst, src, px, hipMemcpyHostToDevice, s);
-        return hipMemcpy2DAsync(dst, (size_t)cols, src, (size_t)step, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice, s);
-    };
-    HIPCHK(upload_rows(fe.g_img.p, in->img, in->step));
+    HIPCHK(upload_rows(s, fe.g_img.p, in->img, cols, rows, in->step));
     if (in->mask)
-        HIPCHK(upload_rows(fe.g_allow.p, in->mask, in->mask_step));
+        HIPCHK(upload_rows(s, fe.g_allow.p, in->mask, cols, rows, in->mask_step));
     else
         HIPCHK(hipMemsetAsync(fe.g_allow.p, 1, px, s));
     if (in->n_exclude > 0)
@@ -545,6 +707,9 @@ int lh_detect_features(lh_handle* h, const lh_detect_input* in, lh_detect_result
 int lh_klt_track(lh_handle* h, const lh_klt_input* in, lh_lk_result* out) { return no_throw(klt_track_impl, h, in, out); }
 int lh_klt_stereo_landmarks(lh_handle* h, const lh_klt_stereo_input* in, lh_stereo_result* out) {
     return no_throw(klt_stereo_landmarks_impl, h, in, out);
+}
+int lh_track_frame(lh_handle* h, const lh_track_input* in, lh_track_result* out) {
+    return no_throw(track_frame_impl, h, in, out);
 }
 
 }  // extern "C"

@@ -82,6 +82,16 @@ struct FrontendState {
     DevBuf<float> g_excl, g_kp;
     DevBuf<lh_gftt_ctl> g_ctl;
     HostBuf<lh_gftt_ctl> s_gctl;   // pinned: read back once per batch of selection rounds
+    // one frame of Frontend::Track (lh_track_frame).  The resident image: two pyramids, rows packed to r_cols bytes and
+    // sized for every level, of which r_img[r_cur] holds the last successful call's img2 with levels 0 .. r_levels - 1
+    // built (r_valid); a call reads it as img1 and makes its own img2 the other one.  No other entry point touches them.
+    DevBuf<uint8_t> r_img[2];
+    int r_cur = 0, r_cols = 0, r_rows = 0, r_levels = 0;
+    bool r_valid = false;
+    // its arenas: one upload (pose, points, keypoints, has_point), one download (pose, counts, kp2, success, the
+    // edge -> feature list, the edges' flags and chi2), and k_frames' inputs as k_track_pack writes them
+    DevBuf<uint8_t> tk_in, tk_out, tk_work;
+    HostBuf<uint8_t> s_tkin, s_tkout;
 };
 
 }  // namespace lh

@@ -1,7 +1,7 @@
 // lh_launch.h — the one declaration of every kernel launcher.  The definitions (lh_lin.hip, lh_kernels.hip and its lh_probe.hip, lh_frames.hip,
-// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip) and the callers (lh_host.cpp, lh_frontend.cpp) all include it: the symbols are extern "C", so only
+// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip, lh_track.hip) and the callers (lh_host.cpp, lh_frontend.cpp) all include it: the symbols are extern "C", so only
 // the compiler, seeing a definition beside this declaration, can tell that the two sides disagree.
-// (lh_tri.h, lh_gftt.h and lh_klt.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.)
+// (lh_tri.h, lh_gftt.h, lh_klt.h and lh_track.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include "lh_gftt.h"
 #include "lh_klt.h"
 #include "lh_lk.h"
+#include "lh_track.h"
 #include "lh_tri.h"
 
 extern "C" {
@@ -63,4 +64,6 @@ hipError_t lh_launch_triangulate(hipStream_t st, const lh_tri_args* a);
 hipError_t lh_launch_gftt_front(hipStream_t st, const lh_gftt_args* a);
 hipError_t lh_launch_gftt_rounds(hipStream_t st, const lh_gftt_args* a, int first, int count);
 hipError_t lh_launch_gftt_order(hipStream_t st, const lh_gftt_args* a);
+hipError_t lh_launch_track_guess(hipStream_t st, const lh_track_args* a);
+hipError_t lh_launch_track_pack(hipStream_t st, const lh_track_args* a);
 }

@@ -233,6 +233,17 @@ class LhKltStereoInput(C.Structure):
     _fields_ = [("klt", LhKltInput)] + LhStereoInput._fields_[1:]
 
 
+class LhTrackInput(C.Structure):
+    _fields_ = [("klt", LhKltInput), ("pts_w", C.c_void_p), ("has_point", C.c_void_p), ("pose_Tcw", C.c_double * 12),
+                ("cam_ext", C.c_double * 12), ("K", C.c_double * 4)]
+
+
+class LhTrackResult(C.Structure):
+    _fields_ = [("kp2", C.c_void_p), ("success", C.c_void_p), ("pose_Tcw", C.c_double * 12), ("is_outlier", C.c_void_p),
+                ("edge_chi2", C.c_void_p), ("n_tracked", C.c_int32), ("n_edges", C.c_int32), ("n_inliers", C.c_int32),
+                ("iterations", C.c_int32), ("time_ms", C.c_double)]
+
+
 class LhDetectInput(C.Structure):
     _fields_ = [
         ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int64), ("img", C.c_void_p), ("mask", C.c_void_p),
@@ -261,7 +272,7 @@ ABI_SYMBOLS = [
     "lh_create", "lh_destroy", "lh_solve", "lh_upload", "lh_solve_resident",
     "lh_kernel_stats_get", "lh_kernel_stats_reset", "lh_classify_outliers", "lh_set_profiling",
     "lh_estimate_pose", "lh_lk_track", "lh_triangulate", "lh_stereo_landmarks", "lh_detect_features",
-    "lh_klt_track", "lh_klt_stereo_landmarks",
+    "lh_klt_track", "lh_klt_stereo_landmarks", "lh_track_frame",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
     "lh_debug_batch", "lh_debug_reduced_system",
@@ -302,6 +313,8 @@ def ba_lib():
         if hasattr(lib, "lh_klt_track"):
             lib.lh_klt_track.argtypes = [C.c_void_p, C.POINTER(LhKltInput), C.POINTER(LhLkResult)]
             lib.lh_klt_stereo_landmarks.argtypes = [C.c_void_p, C.POINTER(LhKltStereoInput), C.POINTER(LhStereoResult)]
+        if hasattr(lib, "lh_track_frame"):
+            lib.lh_track_frame.argtypes = [C.c_void_p, C.POINTER(LhTrackInput), C.POINTER(LhTrackResult)]
         lib.lh_classify_outliers.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lh_debug_event_floor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -639,6 +652,41 @@ class Solver:
         out["success"] = ok.astype(bool)
         out["n_accepted"], out["time_ms"] = r.n_accepted, r.time_ms
         return out
+
+    def track_frame(self, img_last, img_cur, kp1, pts_w, has_point, pose, K, cam_ext=None, want_outlier=True,
+                    want_chi2=True, max_level=3, max_iters=30, epsilon=0.01, min_eig=1e-4):
+        """One frame of Frontend::Track (frontend_lego.cpp:48-75) through lh_track_frame: the guesses from the map
+        points pts_w [n, 3] at the predicted pose [12] (kp1 where has_point [n] is zero; has_point None: every feature
+        has a point), klt_track img_last -> img_cur with them, then estimate_pose on the tracked features with a point.
+        img_last None: the img_cur of the last track_frame on this solver.  cam_ext [12]: the left camera's extrinsic
+        (default identity).  Returns dict(kp2, success, pose_Tcw [12], is_outlier [n] bool and edge_chi2 [n] by feature
+        (None when not wanted), n_tracked, n_edges, n_inliers, iterations, time_ms)."""
+        cur = np.asarray(img_cur)
+        if img_last is None:   # _klt_input takes two images of one layout
+            a, _keep, k2, ok = self._klt_input(cur, cur, kp1, None, max_level, max_iters, epsilon, min_eig)
+            a.img1 = None
+        else:
+            a, _keep, k2, ok = self._klt_input(img_last, cur, kp1, None, max_level, max_iters, epsilon, min_eig)
+        n = a.n_points
+        keep = dict(pts=_as(pts_w, np.float64), hp=_as(has_point, np.uint8))
+        if (keep["pts"] is not None and keep["pts"].size != 3 * n) or (keep["hp"] is not None and keep["hp"].size != n):
+            raise ValueError("pts_w must be [n, 3] and has_point [n]")
+        s = LhTrackInput()
+        s.klt, s.pts_w, s.has_point = a, _ptr(keep["pts"]), _ptr(keep["hp"])
+        ext = np.array([1.0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]) if cam_ext is None else np.asarray(cam_ext, np.float64).reshape(12)
+        p = np.asarray(pose, np.float64).reshape(12)
+        for i in range(12):
+            s.pose_Tcw[i], s.cam_ext[i] = p[i], ext[i]
+        for i in range(4):
+            s.K[i] = float(K[i])
+        flag = np.zeros(n, np.uint8) if want_outlier else None
+        chi2 = np.zeros(n) if want_chi2 else None
+        r = LhTrackResult()
+        r.kp2, r.success, r.is_outlier, r.edge_chi2 = _ptr(k2), _ptr(ok), _ptr(flag), _ptr(chi2)
+        _check(ba_lib().lh_track_frame(self.h, C.byref(s), C.byref(r)), "lh_track_frame")
+        return dict(kp2=k2, success=ok.astype(bool), pose_Tcw=np.array(r.pose_Tcw[:]),
+                    is_outlier=None if flag is None else flag.astype(bool), edge_chi2=chi2, n_tracked=r.n_tracked,
+                    n_edges=r.n_edges, n_inliers=r.n_inliers, iterations=r.iterations, time_ms=r.time_ms)
 
     def detect_features(self, img, exclude=None, mask=None, max_corners=150, quality=0.01, min_distance=20.0,
                         want_eig=False, exclude_half=10.0, capacity=None):
