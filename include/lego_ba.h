@@ -23,6 +23,8 @@
  *     LKOpticalFlow4Layer / 1Layer  algorithm.cpp:11-206      lh_lk_track
  *     cv::calcOpticalFlowPyrLK      frontend_lego.cpp:383-463 lh_klt_track, lh_klt_stereo_landmarks (the live trackers)
  *     Frontend::Track               frontend_lego.cpp:48-75   lh_track_frame (guesses, KLT, selection, pose: one call per frame)
+ *     Frontend::InsertKeyframe      frontend_lego.cpp:77-102  lh_insert_keyframe (DetectFeatures, the right-image KLT and
+ *     Frontend::StereoInit          frontend_lego.cpp:323-362                     TriangulateNewPoints: one call per keyframe)
  *     triangulation                 algorithm.h:11-34         lh_triangulate (batched)
  *     Frontend::TriangulateNewPoints frontend_lego.cpp:111-155 lh_stereo_landmarks (LK left -> right + triangulation,
  *     Frontend::BuildInitMap        frontend_lego.cpp:323-362                       one call per stereo frame)
@@ -324,6 +326,7 @@ int lh_lk_track(lh_handle *h, const lh_lk_input *in, lh_lk_result *out);
  *   bit 2  gate: !(pt[1] <= y_max)                                    frontend_lego.cpp:134
  *   bit 3  gate: !(pt[2] > z_min && pt[2] <= z_max)                   frontend_lego.cpp:135
  *   bit 4  lh_stereo_landmarks: the LK track failed; the point is not triangulated (pt = 0)
+ *   bit 5  lh_insert_keyframe (LH_TRI_F_HAS_POINT): the feature already has a map point; not triangulated (pt = 0)
  * Every test is evaluated (the reference stops at its first failure, so a rejected point may carry several bits),
  * the gate on pt before T_out.  With T_out and flags == 0, pt <- T_out * pt (current_pose_Twc * pworld, :138);
  * a rejected point keeps its untransformed value.
@@ -567,6 +570,83 @@ typedef struct lh_track_result {
     double time_ms;           /* HIP-event bracket, first kernel to last, copies excluded */
 } lh_track_result;
 int lh_track_frame(lh_handle *h, const lh_track_input *in, lh_track_result *out);
+
+/*
+ * A keyframe's half of the frame without a host step in between: Frontend::InsertKeyframe (src/frontend_lego.cpp:77-102)
+ * and StereoInit / BuildInitMap (:323-362) run DetectFeatures (:292-310), the right-image guesses and
+ * cv::calcOpticalFlowPyrLK left -> right (FindFeaturesInRightLKOpticalFlowOpenCV, :423-463) and TriangulateNewPoints
+ * (:111-155).  One upload besides the image(s), one download; the host waits only where lh_detect_features already does
+ * (between batches of selection rounds) and at the end.  The call is defined by the composition it equals bit for bit:
+ *
+ *   detect       corners c_0 .. c_{m-1}: lh_detect_features on the left image with mask = NULL, exclude_pt = have_kp
+ *                (n_exclude = n_have) and this call's exclude_half, max_corners, quality_level and min_distance; m is its
+ *                n_corners (at most max_corners), the order is its order.  n_candidates and lambda_max are its outputs.
+ *   features     n = n_have + m; kl = have_kp followed by the corners, the order features_left_ has after DetectFeatures.
+ *                Feature i < n_have has a point when have_point[i] != 0 (have_point NULL: always); a corner has none.
+ *   guess        with a point: lh_track_frame's guess arithmetic on X = have_pts_w[i], T = pose_Tcw, E = cam_pose[1],
+ *                K = cam_K[1] (camera_right_->world2pixel, :432).  Without: kl[i] (:436).
+ *   track        lh_klt_track(img_left, img_right, kl, the guesses, has_initial = 1) with this call's tracker parameters:
+ *                kp_right and success are bitwise its kp2 and success.  n_right counts success (num_good_pts).
+ *   triangulate  a feature with success and no point (:116-117): pt and flags are bitwise lh_triangulate's on the two
+ *                views ((double)kl[i], (double)kp_right[i]) with cam_pose, cam_K, sing_ratio_thr, the gate and T_out,
+ *                as lh_klt_stereo_landmarks returns them.  A failed track without a point carries flag bit 4 alone; a
+ *                feature that has a point carries bit 5 (LH_TRI_F_HAS_POINT) alone, tracked or not.  Both have pt = 0.
+ *                n_accepted counts flags == 0.
+ *
+ * The resident image is lh_track_frame's.  img_left == NULL reads it: LH_E_STATE if there is none or its cols / rows
+ * differ; the image stays resident and unchanged (the next lh_track_frame with klt.img1 == NULL still finds it), and
+ * the pyramid levels this call's max_level needs beyond those already built are built and remembered.  A non-NULL
+ * img_left is uploaded and becomes the resident image: StereoInit's call (n_have = 0, T_out = NULL) replaces the priming
+ * call.  An argument error or LH_E_STATE leaves the resident image as it was, and so does a failure to
+ * allocate the call's own buffers; a call that fails after it began to enqueue, or while it makes room for a given
+ * img_left, invalidates it.  n_have == 0 with no corner found is LH_OK with every count 0.
+ *
+ * The per-feature outputs have room for n_have + max_corners entries; the first n_have + n_new are written.
+ *
+ * LH_E_BADARG: lh_detect_features' and lh_klt_track's argument errors (cols < 12 or rows < 12, rows * cols > INT32_MAX,
+ * step < cols, a negative or NaN quality_level or min_distance, max_level outside 0..3, max_iters < 1, an epsilon that
+ * is not > 0, a min_eig_threshold that is not >= 0), max_corners <= 0, n_have < 0, a null img_right, a null have_kp with
+ * n_have > 0, a null have_pts_w when some feature can have a point, a null output array, n_have + max_corners > 2^24.
+ */
+typedef struct lh_keyframe_input {
+    int32_t cols, rows;
+    int64_t step;               /* bytes per row of img_right, and of img_left when given (>= cols) */
+    const uint8_t *img_left;    /* [rows][step] current_frame_->left_img_; NULL: the resident image */
+    const uint8_t *img_right;   /* [rows][step] current_frame_->right_img_ */
+    int32_t n_have;
+    const float *have_kp;       /* [n_have][2] current_frame_->features_left_ positions */
+    const double *have_pts_w;   /* [n_have][3] mp->pos_ of each; read only where have_point */
+    const uint8_t *have_point;  /* [n_have] nonzero: the feature has a map point; NULL: every one has */
+    float exclude_half;         /* the detector's, as lh_detect_input's: 10 */
+    int32_t max_corners;        /* > 0: num_features_ (gftt_'s limit, :16), however many features the frame has */
+    double quality_level;       /* 0.01 */
+    double min_distance;        /* 20 */
+    int32_t max_level;          /* the tracker's, as lh_klt_input's: 3 */
+    int32_t max_iters;          /* 30 */
+    double epsilon;             /* 0.01 */
+    double min_eig_threshold;   /* 1e-4 */
+    double pose_Tcw[12];        /* current_frame_->Pose() */
+    double cam_pose[2][12];     /* camera_left_->pose(), camera_right_->pose() */
+    double cam_K[2][4];         /* fx, fy, cx, cy of the two cameras */
+    double sing_ratio_thr;      /* the triangulation's, as lh_stereo_input's */
+    int32_t gate;
+    double y_max, z_min, z_max;
+    const double *T_out;        /* [12] or NULL */
+} lh_keyframe_input;
+typedef struct lh_keyframe_result {
+    float *kp_new;              /* [max_corners][2] the detected corners (required) */
+    float *kp_right;            /* [n_have + max_corners][2] (required, as the three below) */
+    uint8_t *success;           /* [n_have + max_corners] */
+    double *pt;                 /* [n_have + max_corners][3] */
+    uint8_t *flags;             /* [n_have + max_corners] */
+    int32_t n_new;              /* m */
+    int32_t n_candidates;
+    double lambda_max;
+    int32_t n_right;            /* num_good_pts (:454-461) */
+    int32_t n_accepted;         /* cnt_triangulated_pts (:146) */
+    double time_ms;             /* HIP-event bracket, first kernel to last: the detector's host checks included, copies excluded */
+} lh_keyframe_result;
+int lh_insert_keyframe(lh_handle *h, const lh_keyframe_input *in, lh_keyframe_result *out);
 
 /* ---- test hooks (not part of the reference interface) ---- */
 /* f64 MFMA accumulator-layout probe: D(16x16) = A(16x4) * B(4x16), device pointers, row-major */

@@ -1,6 +1,6 @@
 // lh_frontend.cpp — the frontend entry points of the C ABI (include/lego_ba.h) on the solver's handle and stream:
 // lh_estimate_pose, lh_lk_track, lh_klt_track, lh_triangulate, lh_stereo_landmarks, lh_klt_stereo_landmarks,
-// lh_detect_features, lh_track_frame.  Each checks its arguments,
+// lh_detect_features, lh_track_frame, lh_insert_keyframe.  Each checks its arguments,
 // grows its buffers (lh_handle.h FrontendState), enqueues copies and kernels, synchronises and copies out.
 #include <cmath>
 
@@ -228,17 +228,20 @@ int lk_track_impl(lh_handle* h, const lh_lk_input* in, lh_lk_result* out) {
 // The fields lh_triangulate and lh_stereo_landmarks share: threshold, gate, T_out, and the output arena
 // (pt [n][3], sing_ratio [n], flags [n]).
 struct TriOut { size_t o_ratio, o_flag, o_end; };
+void tri_tests(lh_tri_args* a, double thr, int gate, double y_max, double z_min, double z_max, const double* T_out) {
+    a->thr = thr;
+    a->gate = gate ? 1 : 0;
+    a->y_max = y_max; a->z_min = z_min; a->z_max = z_max;
+    a->has_T = T_out ? 1 : 0;
+    for (int i = 0; i < 12; ++i) a->T[i] = T_out ? T_out[i] : 0.0;
+}
 int tri_outputs(lh_handle* h, lh_tri_args* a, int n, double thr, int gate, double y_max, double z_min,
                 double z_max, const double* T_out, TriOut* o) {
     o->o_ratio = sizeof(double) * 3 * (size_t)n;
     o->o_flag = o->o_ratio + sizeof(double) * (size_t)n;
     o->o_end = o->o_flag + (size_t)n;
     HIPCHK(h->fe.t_out.ensure(o->o_end));
-    a->thr = thr;
-    a->gate = gate ? 1 : 0;
-    a->y_max = y_max; a->z_min = z_min; a->z_max = z_max;
-    a->has_T = T_out ? 1 : 0;
-    for (int i = 0; i < 12; ++i) a->T[i] = T_out ? T_out[i] : 0.0;
+    tri_tests(a, thr, gate, y_max, z_min, z_max, T_out);
     a->pt = (double*)h->fe.t_out.p;
     a->ratio = (double*)(h->fe.t_out.p + o->o_ratio);
     a->flags = h->fe.t_out.p + o->o_flag;
@@ -608,6 +611,52 @@ int track_frame_impl(lh_handle* h, const lh_track_input* in, lh_track_result* ou
 // corners, defined in exact arithmetic (lh_gftt.h).  The image, lambda and every list stay on
 // the device; the host reads one lh_gftt_ctl per batch of selection rounds, to know when none is left open.
 #define LH_GFTT_ROUND_BATCH 8   // a round that finds nothing open costs a launch; a check costs a synchronise
+
+// The detector's working buffers for a cols x rows image and `limit` corners, and its arguments but for the image, the
+// exclusion list and the corner list, which are the caller's (lh_insert_keyframe has all three elsewhere).
+int gftt_prepare(FrontendState& fe, int cols, int rows, double quality_level, double min_distance, int limit, lh_gftt_args* a) {
+    const size_t px = (size_t)rows * (size_t)cols;
+    HIPCHK(fe.g_allow.ensure(px));
+    HIPCHK(fe.g_state.ensure(px + 4));   // k_gftt_round reads it by aligned words
+    HIPCHK(fe.g_eig.ensure(px));
+    HIPCHK(fe.g_cand.ensure(px));
+    HIPCHK(fe.g_acc_idx.ensure(px));
+    HIPCHK(fe.g_acc_lam.ensure(px));
+    HIPCHK(fe.g_resp.ensure((size_t)std::max(limit, 1)));
+    HIPCHK(fe.g_ctl.ensure(1));
+    HIPCHK(fe.s_gctl.ensure(1));
+    a->cols = cols; a->rows = rows;
+    a->allow = fe.g_allow.p;
+    a->quality = quality_level;
+    a->min_dist2 = min_distance * min_distance;
+    // candidates nearer than min_distance differ by at most ceil(min_distance) - 1 pixels along an axis
+    a->reach = min_distance < 1.0 ? -1 : (int)std::min(std::ceil(min_distance) - 1.0, (double)std::max(cols, rows));
+    a->limit = limit;
+    a->eig = fe.g_eig.p; a->state = fe.g_state.p; a->cand = fe.g_cand.p;
+    a->acc_idx = fe.g_acc_idx.p; a->acc_lam = fe.g_acc_lam.p;
+    a->response = fe.g_resp.p; a->ctl = fe.g_ctl.p;
+    return LH_OK;
+}
+
+// The detector's kernels on an image, an allow image and a zeroed lh_gftt_ctl that are on the device: the front, the
+// selection rounds in batches with a read of the control block after each, the ordered corner list.  On return the
+// stream has drained up to the last batch of rounds; k_gftt_accepted and k_gftt_rank are enqueued behind it.
+int gftt_select(FrontendCall& call, const lh_gftt_args& a) {
+    hipStream_t s = call.s;
+    FrontendState& fe = call.h->fe;
+    HIPCHK(lh_launch_gftt_front(s, &a));
+    const lh_gftt_ctl& ctl = *fe.s_gctl.p;
+    if (a.reach >= 0)
+        for (int r = 0;; r += LH_GFTT_ROUND_BATCH) {   // a round decides at least the strongest open candidate
+            HIPCHK(lh_launch_gftt_rounds(s, &a, r, LH_GFTT_ROUND_BATCH));
+            HIPCHK(hipMemcpyAsync(fe.s_gctl.p, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (ctl.open[(r + LH_GFTT_ROUND_BATCH - 1) % 3] == 0) break;
+        }
+    HIPCHK(lh_launch_gftt_order(s, &a));
+    return LH_OK;
+}
+
 int detect_features_impl(lh_handle* h, const lh_detect_input* in, lh_detect_result* out) {
     if (!h || !in || !out || !in->img) return LH_E_BADARG;
     const int cols = in->cols, rows = in->rows;
@@ -626,18 +675,11 @@ int detect_features_impl(lh_handle* h, const lh_detect_input* in, lh_detect_resu
     FrontendState& fe = h->fe;
     const size_t px = (size_t)rows * (size_t)cols;
     const int limit = in->max_corners > 0 ? in->max_corners : out->kp_capacity;
+    lh_gftt_args a{};
+    STAGE(gftt_prepare(fe, cols, rows, in->quality_level, in->min_distance, limit, &a));
     HIPCHK(fe.g_img.ensure(px));
-    HIPCHK(fe.g_allow.ensure(px));
-    HIPCHK(fe.g_state.ensure(px + 4));   // k_gftt_round reads it by aligned words
-    HIPCHK(fe.g_eig.ensure(px));
-    HIPCHK(fe.g_cand.ensure(px));
-    HIPCHK(fe.g_acc_idx.ensure(px));
-    HIPCHK(fe.g_acc_lam.ensure(px));
     HIPCHK(fe.g_excl.ensure(2 * (size_t)std::max(in->n_exclude, 1)));
     HIPCHK(fe.g_kp.ensure(2 * (size_t)std::max(limit, 1)));
-    HIPCHK(fe.g_resp.ensure((size_t)std::max(limit, 1)));
-    HIPCHK(fe.g_ctl.ensure(1));
-    HIPCHK(fe.s_gctl.ensure(1));
     HIPCHK(upload_rows(s, fe.g_img.p, in->img, cols, rows, in->step));
     if (in->mask)
         HIPCHK(upload_rows(s, fe.g_allow.p, in->mask, cols, rows, in->mask_step));
@@ -646,30 +688,13 @@ int detect_features_impl(lh_handle* h, const lh_detect_input* in, lh_detect_resu
     if (in->n_exclude > 0)
         HIPCHK(hipMemcpyAsync(fe.g_excl.p, in->exclude_pt, 2 * sizeof(float) * (size_t)in->n_exclude, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(fe.g_ctl.p, 0, sizeof(lh_gftt_ctl), s));
-    lh_gftt_args a{};
-    a.cols = cols; a.rows = rows;
-    a.img = fe.g_img.p; a.allow = fe.g_allow.p;
+    a.img = fe.g_img.p;
     a.n_exclude = in->n_exclude; a.exclude_pt = fe.g_excl.p; a.exclude_half = in->exclude_half;
-    a.quality = in->quality_level;
-    a.min_dist2 = in->min_distance * in->min_distance;
-    // candidates nearer than min_distance differ by at most ceil(min_distance) - 1 pixels along an axis
-    a.reach = in->min_distance < 1.0 ? -1 : (int)std::min(std::ceil(in->min_distance) - 1.0, (double)std::max(cols, rows));
-    a.limit = limit;
-    a.eig = fe.g_eig.p; a.state = fe.g_state.p; a.cand = fe.g_cand.p;
-    a.acc_idx = fe.g_acc_idx.p; a.acc_lam = fe.g_acc_lam.p;
-    a.kp = fe.g_kp.p; a.response = fe.g_resp.p; a.ctl = fe.g_ctl.p;
+    a.kp = fe.g_kp.p;
     STAGE(call.start());
-    HIPCHK(lh_launch_gftt_front(s, &a));
-    const lh_gftt_ctl& ctl = *fe.s_gctl.p;
-    if (a.reach >= 0)
-        for (int r = 0;; r += LH_GFTT_ROUND_BATCH) {   // a round decides at least the strongest open candidate
-            HIPCHK(lh_launch_gftt_rounds(s, &a, r, LH_GFTT_ROUND_BATCH));
-            HIPCHK(hipMemcpyAsync(fe.s_gctl.p, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (ctl.open[(r + LH_GFTT_ROUND_BATCH - 1) % 3] == 0) break;
-        }
-    HIPCHK(lh_launch_gftt_order(s, &a));
+    STAGE(gftt_select(call, a));
     STAGE(call.stop());
+    const lh_gftt_ctl& ctl = *fe.s_gctl.p;
     HIPCHK(hipMemcpyAsync(fe.s_gctl.p, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
     if (out->eig) HIPCHK(hipMemcpyAsync(out->eig, a.eig, sizeof(double) * px, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -684,6 +709,158 @@ int detect_features_impl(lh_handle* h, const lh_detect_input* in, lh_detect_resu
     out->n_corners = in->max_corners > 0 ? (int32_t)n_written : (int32_t)ctl.n_acc;
     out->n_candidates = (int32_t)ctl.n_cand;
     out->lambda_max = ctl.max_key ? lh_gftt_unkey(ctl.max_key) : 0.0;
+    return LH_OK;
+}
+
+// Frontend::InsertKeyframe's and StereoInit's chain (frontend_lego.cpp:77-102, :323-362) in one call (include/lego_ba.h,
+// DESIGN.md 2.5e): upload img_right (and img_left, unless the resident image stands in for it) and one arena; the
+// detector on level 0 of the resident pyramid, k_kf_assemble, the tracker's kernels, k_triangulate and k_kf_finish behind
+// one another on the device buffers; one download.  The corner count stays on the device until then: every launch
+// behind the detector is sized for n_have + max_corners slots (lh_keyframe.h).  The host waits where the detector
+// always has, between batches of selection rounds, and once at the end.
+int insert_keyframe_impl(lh_handle* h, const lh_keyframe_input* in, lh_keyframe_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    const int cols = in->cols, rows = in->rows, nh = in->n_have, mc = in->max_corners;
+    // lh_detect_features' argument errors (mask == NULL), then lh_klt_track's
+    if (cols < 3 || rows < 3 || in->step < cols || (int64_t)rows * cols > INT32_MAX) return LH_E_BADARG;
+    if (nh < 0 || (nh > 0 && !in->have_kp) || mc <= 0 || (int64_t)nh + mc > LH_KF_MAX_FEATURES) return LH_E_BADARG;
+    if (!(in->quality_level >= 0.0) || !(in->min_distance >= 0.0)) return LH_E_BADARG;
+    if (!in->img_right || !out->kp_new || !out->kp_right || !out->success || !out->pt || !out->flags) return LH_E_BADARG;
+    const int cap = nh + mc;
+    lh_klt_input k{};
+    k.cols = cols; k.rows = rows; k.step = in->step;
+    k.img1 = k.img2 = in->img_right;   // a null img_left is the resident image
+    k.n_points = cap;
+    k.kp1 = out->kp_right;             // (the list is made on the device: any non-null pointer passes the check)
+    k.max_level = in->max_level; k.max_iters = in->max_iters;
+    k.epsilon = in->epsilon; k.min_eig_threshold = in->min_eig_threshold;
+    STAGE(klt_check(&k, out->kp_right, out->success));
+    if (nh > 0 && !in->have_pts_w) {
+        if (!in->have_point) return LH_E_BADARG;
+        for (int i = 0; i < nh; ++i)
+            if (in->have_point[i]) return LH_E_BADARG;
+    }
+    FrontendState& fe = h->fe;
+    if (!in->img_left && !(fe.r_valid && fe.r_cols == cols && fe.r_rows == rows)) return LH_E_STATE;
+    out->n_new = out->n_candidates = out->n_right = out->n_accepted = 0;
+    out->lambda_max = 0.0;
+    out->time_ms = 0.0;
+    FrontendCall call(h);
+    STAGE(call.select());
+    hipStream_t s = call.s;
+    const int slot = fe.r_cur;
+    const int have_I = in->img_left ? 1 : fe.r_levels;   // the left pyramid's first level to build
+    lh_klt_levels full{};   // as lh_track_frame: the pyramid buffers hold every level, whatever max_level a call asks for
+    const int n_full = lh_klt_level_sizes(cols, rows, LH_KLT_MAX_LEVELS - 1, full.cols, full.rows);
+    const size_t pyr_bytes = (size_t)klt_pyramid_layout(&full, n_full, nullptr, cols);
+    HIPCHK(fe.kf_right.ensure(pyr_bytes));
+    // arena layouts (16-byte aligned segments).  The upload ends with have_kp, the head of the feature list, and the
+    // device arena goes on for the corners behind it
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t NH = (size_t)nh, CAP = (size_t)cap;
+    const size_t i_cam = 0, i_K = sizeof(double) * 24, i_pts = i_K + sizeof(double) * 8,
+                 i_hp = i_pts + al(sizeof(double) * 3 * NH), i_kl = i_hp + (in->have_point ? al(NH) : 0),
+                 i_up = i_kl + sizeof(float) * 2 * NH, i_end = i_kl + sizeof(float) * 2 * CAP;
+    const size_t o_cnt = 0, o_lam = sizeof(int32_t) * 4, o_pt = 32, o_kpr = o_pt + al(sizeof(double) * 3 * CAP),
+                 o_new = o_kpr + al(sizeof(float) * 2 * CAP), o_succ = o_new + al(sizeof(float) * 2 * (size_t)mc),
+                 o_flag = o_succ + al(CAP), o_end = o_flag + al(CAP);
+    HIPCHK(fe.kf_in.ensure(i_end));
+    HIPCHK(fe.kf_out.ensure(o_end));
+    HIPCHK(fe.kf_state.ensure(CAP));
+    HIPCHK(fe.s_kfin.ensure(i_up));
+    HIPCHK(fe.s_kfout.ensure(o_end));
+    lh_gftt_args g{};
+    STAGE(gftt_prepare(fe, cols, rows, in->quality_level, in->min_distance, mc, &g));
+    // Every buffer of the call's own is there.  From here on the resident image is in the making (a given img_left
+    // replaces it, its buffer first if that has to grow; then the enqueueing begins): valid again once the call has
+    // succeeded.  A resident image that stays has this call's size, and its buffer every level's room.
+    fe.r_valid = false;
+    if (in->img_left) HIPCHK(fe.r_img[slot].ensure(pyr_bytes));
+    lh_klt_args a{};
+    a.n_levels = lh_klt_level_sizes(cols, rows, in->max_level, a.I.cols, a.I.rows);
+    a.J = a.I;
+    klt_pyramid_layout(&a.I, a.n_levels, fe.r_img[slot].p, cols);
+    klt_pyramid_layout(&a.J, a.n_levels, fe.kf_right.p, cols);
+    HIPCHK(upload_rows(s, fe.kf_right.p, in->img_right, cols, rows, in->step));
+    if (in->img_left) HIPCHK(upload_rows(s, fe.r_img[slot].p, in->img_left, cols, rows, in->step));
+    uint8_t *ki = fe.kf_in.p, *ko = fe.kf_out.p;
+    {
+        uint8_t* st = fe.s_kfin.p;
+        const ByteSeg seg[5] = {{st + i_cam, in->cam_pose, sizeof(double) * 24},
+                                {st + i_K, in->cam_K, sizeof(double) * 8},
+                                {st + i_pts, in->have_pts_w, in->have_pts_w ? sizeof(double) * 3 * NH : 0},
+                                {st + i_hp, in->have_point, in->have_point ? NH : 0},
+                                {st + i_kl, in->have_kp, sizeof(float) * 2 * NH}};
+        par_copy(h, seg, 5);
+        HIPCHK(hipMemcpyAsync(ki, st, i_up, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemsetAsync(fe.g_allow.p, 1, (size_t)rows * (size_t)cols, s));
+    HIPCHK(hipMemsetAsync(fe.g_ctl.p, 0, sizeof(lh_gftt_ctl), s));
+    float* kl = (float*)(ki + i_kl);
+    g.img = fe.r_img[slot].p;   // level 0 of the resident pyramid: rows packed to cols, the layout g_img has
+    g.n_exclude = nh; g.exclude_pt = kl; g.exclude_half = in->exclude_half;
+    g.kp = kl + 2 * NH;         // the corners straight into the feature list, behind have_kp
+    lh_kf_args f{};
+    f.n_have = nh; f.max_corners = mc;
+    f.ctl = g.ctl;
+    f.pts_w = (const double*)(ki + i_pts);
+    f.has_point = in->have_point ? ki + i_hp : nullptr;
+    for (int i = 0; i < 12; ++i) { f.pose[i] = in->pose_Tcw[i]; f.ext[i] = in->cam_pose[1][i]; }
+    for (int i = 0; i < 4; ++i) f.K[i] = in->cam_K[1][i];
+    f.kl = kl;
+    f.kp_right = (float*)(ko + o_kpr);
+    f.state = fe.kf_state.p;
+    f.kp_new = (float*)(ko + o_new);
+    f.success = ko + o_succ;
+    f.pt = (double*)(ko + o_pt);
+    f.flags = ko + o_flag;
+    f.counts = (int32_t*)(ko + o_cnt);
+    f.lambda_max = (double*)(ko + o_lam);
+    a.n_points = cap;
+    a.kp1 = kl;
+    a.kp2 = f.kp_right;
+    a.success = ko + o_succ;
+    a.has_initial = 1;
+    a.max_iters = in->max_iters;
+    a.eps2 = in->epsilon * in->epsilon;
+    a.min_eig = in->min_eig_threshold;
+    lh_tri_args t{};
+    tri_tests(&t, in->sing_ratio_thr, in->gate, in->y_max, in->z_min, in->z_max, in->T_out);
+    t.n_points = cap; t.n_poses = 2;
+    t.pose = (const double*)(ki + i_cam);
+    t.cam_K = (const double*)(ki + i_K);
+    t.kp1 = kl; t.kp2 = f.kp_right; t.success = f.success;
+    t.pt = f.pt; t.flags = f.flags;
+    STAGE(call.start());
+    STAGE(gftt_select(call, g));
+    HIPCHK(lh_launch_kf_assemble(s, &f));
+    STAGE(klt_pyr_track(s, a, have_I));
+    HIPCHK(lh_launch_triangulate(s, &t));
+    HIPCHK(lh_launch_kf_finish(s, &f));
+    STAGE(call.stop());
+    HIPCHK(hipMemcpyAsync(fe.s_kfout.p, ko, o_end, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const uint8_t* st = fe.s_kfout.p;
+    const int32_t* cnt = (const int32_t*)(st + o_cnt);
+    const int32_t m = cnt[0];
+    if (m < 0 || m > mc) return LH_E_HIP;
+    const size_t N = NH + (size_t)m;
+    const ByteSeg seg[5] = {{out->kp_new, st + o_new, sizeof(float) * 2 * (size_t)m},
+                            {out->kp_right, st + o_kpr, sizeof(float) * 2 * N},
+                            {out->success, st + o_succ, N},
+                            {out->pt, st + o_pt, sizeof(double) * 3 * N},
+                            {out->flags, st + o_flag, N}};
+    par_copy(h, seg, 5);
+    out->n_new = m;
+    out->n_candidates = cnt[1];
+    out->n_right = cnt[2];
+    out->n_accepted = cnt[3];
+    out->lambda_max = *(const double*)(st + o_lam);
+    STAGE(call.time(&out->time_ms));
+    fe.r_cols = cols;
+    fe.r_rows = rows;
+    fe.r_levels = in->img_left ? a.n_levels : std::max(fe.r_levels, a.n_levels);
+    fe.r_valid = true;
     return LH_OK;
 }
 
@@ -710,6 +887,9 @@ int lh_klt_stereo_landmarks(lh_handle* h, const lh_klt_stereo_input* in, lh_ster
 }
 int lh_track_frame(lh_handle* h, const lh_track_input* in, lh_track_result* out) {
     return no_throw(track_frame_impl, h, in, out);
+}
+int lh_insert_keyframe(lh_handle* h, const lh_keyframe_input* in, lh_keyframe_result* out) {
+    return no_throw(insert_keyframe_impl, h, in, out);
 }
 
 }  // extern "C"

@@ -84,7 +84,8 @@ struct FrontendState {
     HostBuf<lh_gftt_ctl> s_gctl;   // pinned: read back once per batch of selection rounds
     // one frame of Frontend::Track (lh_track_frame).  The resident image: two pyramids, rows packed to r_cols bytes and
     // sized for every level, of which r_img[r_cur] holds the last successful call's img2 with levels 0 .. r_levels - 1
-    // built (r_valid); a call reads it as img1 and makes its own img2 the other one.  No other entry point touches them.
+    // built (r_valid); a call reads it as img1 and makes its own img2 the other one.  lh_insert_keyframe reads it as its
+    // left image, or replaces it with the one it is given; no other entry point touches them.
     DevBuf<uint8_t> r_img[2];
     int r_cur = 0, r_cols = 0, r_rows = 0, r_levels = 0;
     bool r_valid = false;
@@ -92,6 +93,12 @@ struct FrontendState {
     // edge -> feature list, the edges' flags and chi2), and k_frames' inputs as k_track_pack writes them
     DevBuf<uint8_t> tk_in, tk_out, tk_work;
     HostBuf<uint8_t> s_tkin, s_tkout;
+    // a keyframe's half of the frame (lh_insert_keyframe).  Its left image is the resident one above, which the detector
+    // and the tracker read in place; the right image's pyramid (the resident layout) is this call's own.  One upload
+    // arena (the cameras, the features' points and has_point bytes, have_kp with room for the corners behind it: the
+    // feature list), one download arena (counts, pt, kp_right, the corners, success, flags), the slots' states.
+    DevBuf<uint8_t> kf_right, kf_in, kf_out, kf_state;
+    HostBuf<uint8_t> s_kfin, s_kfout;
 };
 
 }  // namespace lh

@@ -1,12 +1,14 @@
 // lh_launch.h — the one declaration of every kernel launcher.  The definitions (lh_lin.hip, lh_kernels.hip and its lh_probe.hip, lh_frames.hip,
-// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip, lh_track.hip) and the callers (lh_host.cpp, lh_frontend.cpp) all include it: the symbols are extern "C", so only
+// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip, lh_track.hip, lh_keyframe.hip) and the callers (lh_host.cpp, lh_frontend.cpp) all include it: the symbols are extern "C", so only
 // the compiler, seeing a definition beside this declaration, can tell that the two sides disagree.
-// (lh_tri.h, lh_gftt.h, lh_klt.h and lh_track.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.)
+// (lh_tri.h, lh_gftt.h, lh_klt.h and lh_track.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.
+// lh_keyframe.h holds its kernels' arguments alone, and no HIP type either.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "lh_common.h"
 #include "lh_gftt.h"
+#include "lh_keyframe.h"
 #include "lh_klt.h"
 #include "lh_lk.h"
 #include "lh_track.h"
@@ -66,4 +68,6 @@ hipError_t lh_launch_gftt_rounds(hipStream_t st, const lh_gftt_args* a, int firs
 hipError_t lh_launch_gftt_order(hipStream_t st, const lh_gftt_args* a);
 hipError_t lh_launch_track_guess(hipStream_t st, const lh_track_args* a);
 hipError_t lh_launch_track_pack(hipStream_t st, const lh_track_args* a);
+hipError_t lh_launch_kf_assemble(hipStream_t st, const lh_kf_args* a);
+hipError_t lh_launch_kf_finish(hipStream_t st, const lh_kf_args* a);
 }

@@ -21,6 +21,7 @@
 #define LH_TRI_F_Y 4           // gate: !(pt[1] <= y_max)                        frontend_lego.cpp:134
 #define LH_TRI_F_Z 8           // gate: !(pt[2] > z_min && pt[2] <= z_max)       frontend_lego.cpp:135
 #define LH_TRI_F_TRACK 16      // lh_stereo_landmarks: the LK track failed, nothing triangulated
+#define LH_TRI_F_HAS_POINT 32  // lh_insert_keyframe: the feature has a map point already, nothing triangulated (k_kf_finish)
 
 #define LH_TRI_SWEEPS 16       // cap of the Jacobi sweeps (noisy stereo input settles in ~5)
 

@@ -244,6 +244,24 @@ class LhTrackResult(C.Structure):
                 ("iterations", C.c_int32), ("time_ms", C.c_double)]
 
 
+class LhKeyframeInput(C.Structure):
+    _fields_ = [
+        ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int64), ("img_left", C.c_void_p), ("img_right", C.c_void_p),
+        ("n_have", C.c_int32), ("have_kp", C.c_void_p), ("have_pts_w", C.c_void_p), ("have_point", C.c_void_p),
+        ("exclude_half", C.c_float), ("max_corners", C.c_int32), ("quality_level", C.c_double), ("min_distance", C.c_double),
+        ("max_level", C.c_int32), ("max_iters", C.c_int32), ("epsilon", C.c_double), ("min_eig_threshold", C.c_double),
+        ("pose_Tcw", C.c_double * 12), ("cam_pose", C.c_double * 24), ("cam_K", C.c_double * 8),
+        ("sing_ratio_thr", C.c_double), ("gate", C.c_int32), ("y_max", C.c_double), ("z_min", C.c_double),
+        ("z_max", C.c_double), ("T_out", C.c_void_p),
+    ]
+
+
+class LhKeyframeResult(C.Structure):
+    _fields_ = [("kp_new", C.c_void_p), ("kp_right", C.c_void_p), ("success", C.c_void_p), ("pt", C.c_void_p),
+                ("flags", C.c_void_p), ("n_new", C.c_int32), ("n_candidates", C.c_int32), ("lambda_max", C.c_double),
+                ("n_right", C.c_int32), ("n_accepted", C.c_int32), ("time_ms", C.c_double)]
+
+
 class LhDetectInput(C.Structure):
     _fields_ = [
         ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int64), ("img", C.c_void_p), ("mask", C.c_void_p),
@@ -260,6 +278,7 @@ class LhDetectResult(C.Structure):
 
 # lh_tri_result.flags
 LH_TRI_NONFINITE, LH_TRI_RATIO, LH_TRI_Y, LH_TRI_Z, LH_TRI_TRACK = 1, 2, 4, 8, 16
+LH_TRI_HAS_POINT = 32   # lh_keyframe_result.flags: the feature has a map point already
 
 
 class LhKernelStats(C.Structure):
@@ -272,7 +291,7 @@ ABI_SYMBOLS = [
     "lh_create", "lh_destroy", "lh_solve", "lh_upload", "lh_solve_resident",
     "lh_kernel_stats_get", "lh_kernel_stats_reset", "lh_classify_outliers", "lh_set_profiling",
     "lh_estimate_pose", "lh_lk_track", "lh_triangulate", "lh_stereo_landmarks", "lh_detect_features",
-    "lh_klt_track", "lh_klt_stereo_landmarks", "lh_track_frame",
+    "lh_klt_track", "lh_klt_stereo_landmarks", "lh_track_frame", "lh_insert_keyframe",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
     "lh_debug_batch", "lh_debug_reduced_system",
@@ -315,6 +334,8 @@ def ba_lib():
             lib.lh_klt_stereo_landmarks.argtypes = [C.c_void_p, C.POINTER(LhKltStereoInput), C.POINTER(LhStereoResult)]
         if hasattr(lib, "lh_track_frame"):
             lib.lh_track_frame.argtypes = [C.c_void_p, C.POINTER(LhTrackInput), C.POINTER(LhTrackResult)]
+        if hasattr(lib, "lh_insert_keyframe"):
+            lib.lh_insert_keyframe.argtypes = [C.c_void_p, C.POINTER(LhKeyframeInput), C.POINTER(LhKeyframeResult)]
         lib.lh_classify_outliers.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lh_debug_event_floor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -687,6 +708,61 @@ class Solver:
         return dict(kp2=k2, success=ok.astype(bool), pose_Tcw=np.array(r.pose_Tcw[:]),
                     is_outlier=None if flag is None else flag.astype(bool), edge_chi2=chi2, n_tracked=r.n_tracked,
                     n_edges=r.n_edges, n_inliers=r.n_inliers, iterations=r.iterations, time_ms=r.time_ms)
+
+    def insert_keyframe(self, img_left, img_right, have_kp, have_pts_w, have_point, pose, cam_pose, cam_K, max_corners=150,
+                        quality=0.01, min_distance=20.0, exclude_half=10.0, max_level=3, max_iters=30, epsilon=0.01,
+                        min_eig=1e-4, thr=1e-3, gate=None, T_out=None):
+        """Frontend::InsertKeyframe's chain (frontend_lego.cpp:77-102; StereoInit's with no feature yet) through
+        lh_insert_keyframe: detect_features on img_left outside the boxes around have_kp [n_have, 2], the right-image
+        guesses (the map points have_pts_w [n_have, 3] through the right camera where have_point [n_have] is nonzero;
+        None: everywhere), klt_track left -> right on have_kp followed by the new corners, and the triangulation of the
+        tracked features without a point.  img_left None: the resident image of track_frame; an image given becomes it.
+        pose [12]: the frame's T_cw; cam_pose [2, 12] and cam_K [2, 4]: the left and right cameras.
+        Returns dict(kp_new [n_new, 2], kp_right [n, 2], success [n] bool, pt [n, 3], flags [n] uint8 with
+        n = n_have + n_new, n_new, n_candidates, lambda_max, n_right, n_accepted, time_ms)."""
+        def rows_ok(a):
+            return a.ndim == 2 and a.dtype == np.uint8 and a.strides[1] == 1 and a.strides[0] >= a.shape[1]
+        right = np.asarray(img_right)
+        left = None if img_left is None else np.asarray(img_left)
+        if not rows_ok(right) or (left is not None and not (rows_ok(left) and left.strides == right.strides)):
+            right = np.ascontiguousarray(img_right, dtype=np.uint8)
+            left = None if img_left is None else np.ascontiguousarray(img_left, dtype=np.uint8)
+        if right.ndim != 2 or (left is not None and left.shape != right.shape):
+            raise ValueError("images must be 2-D uint8 arrays of one shape")
+        keep = dict(kp=np.ascontiguousarray(np.zeros((0, 2)) if have_kp is None else have_kp, dtype=np.float32).reshape(-1, 2),
+                    pts=_as(have_pts_w, np.float64), hp=_as(have_point, np.uint8))
+        nh = keep["kp"].shape[0]
+        if (keep["pts"] is not None and keep["pts"].size != 3 * nh) or (keep["hp"] is not None and keep["hp"].size != nh):
+            raise ValueError("have_pts_w must be [n_have, 3] and have_point [n_have]")
+        s = LhKeyframeInput()
+        s.rows, s.cols = right.shape
+        s.step = right.strides[0]
+        s.img_left, s.img_right = _ptr(left), _ptr(right)
+        s.n_have, s.have_kp = nh, _ptr(keep["kp"]) if nh else None
+        s.have_pts_w, s.have_point = _ptr(keep["pts"]), _ptr(keep["hp"])
+        s.exclude_half, s.max_corners = float(exclude_half), int(max_corners)
+        s.quality_level, s.min_distance = float(quality), float(min_distance)
+        s.max_level, s.max_iters, s.epsilon, s.min_eig_threshold = int(max_level), int(max_iters), float(epsilon), float(min_eig)
+        p = np.asarray(pose, np.float64).reshape(12)
+        cp, ck = np.asarray(cam_pose, np.float64).reshape(24), np.asarray(cam_K, np.float64).reshape(8)
+        for i in range(12):
+            s.pose_Tcw[i] = p[i]
+        for i in range(24):
+            s.cam_pose[i] = cp[i]
+        for i in range(8):
+            s.cam_K[i] = ck[i]
+        self._tri_common(s, keep, thr, gate, T_out)
+        cap = nh + max(int(max_corners), 0)
+        kp_new = np.zeros((max(int(max_corners), 0), 2), np.float32)
+        kpr, ok = np.zeros((cap, 2), np.float32), np.zeros(cap, np.uint8)
+        pt, flags = np.zeros((cap, 3)), np.zeros(cap, np.uint8)
+        r = LhKeyframeResult()
+        r.kp_new, r.kp_right, r.success, r.pt, r.flags = _ptr(kp_new), _ptr(kpr), _ptr(ok), _ptr(pt), _ptr(flags)
+        _check(ba_lib().lh_insert_keyframe(self.h, C.byref(s), C.byref(r)), "lh_insert_keyframe")
+        n = nh + r.n_new
+        return dict(kp_new=kp_new[:r.n_new], kp_right=kpr[:n], success=ok[:n].astype(bool), pt=pt[:n], flags=flags[:n],
+                    n_new=r.n_new, n_candidates=r.n_candidates, lambda_max=r.lambda_max, n_right=r.n_right,
+                    n_accepted=r.n_accepted, time_ms=r.time_ms)
 
     def detect_features(self, img, exclude=None, mask=None, max_corners=150, quality=0.01, min_distance=20.0,
                         want_eig=False, exclude_half=10.0, capacity=None):
