@@ -55,7 +55,8 @@ typedef enum lh_status {
     LH_E_HIP = 3,         /* HIP runtime error (device missing, OOM, launch failure)                    */
     LH_E_RCCL = 4,        /* RCCL communicator / collective error                                       */
     LH_E_UNSUPPORTED = 5, /* window outside the supported envelope (see DESIGN.md "Limits")            */
-    LH_E_STATE = 6        /* call out of order (e.g. lh_solve_resident before lh_upload)               */
+    LH_E_STATE = 6,       /* call out of order (e.g. lh_solve_resident before lh_upload)               */
+    LH_E_SINGULAR = 7     /* lh_covariance: no free pose, a non-positive pivot, rank-deficient landmarks */
 } lh_status;
 
 /* Problem::StrategyType (problem.h:45-50) */
@@ -647,6 +648,45 @@ typedef struct lh_keyframe_result {
     double time_ms;             /* HIP-event bracket, first kernel to last: the detector's host checks included, copies excluded */
 } lh_keyframe_result;
 int lh_insert_keyframe(lh_handle *h, const lh_keyframe_input *in, lh_keyframe_result *out);
+
+/* ---- marginal covariances of a solved window (g2o's computeMarginals, Ceres' Covariance) ----
+ *
+ * lh_covariance works on the state the last lh_solve / lh_solve_resident on the handle returned (lh_result's poses and
+ * landmarks), with the handle's weights and gate: Huber(huber_delta), gate_mode, precision; the information of an
+ * observation is the identity in pixels, as the reference sets it.  With H the Gauss-Newton Hessian at that state
+ * (H_pp, H_pl, H_ll as the solver forms them; no lambda) and S = H_pp - H_pl H_ll^-1 H_lp:
+ *
+ *   held poses   the window's fixed poses, and pose `anchor` when anchor >= 0; f: the six rows of every other pose;
+ *   Sigma_pp     [f, f] = (S[f, f])^-1; every row and column of a held pose is +0.0.  The covariance of the left
+ *                perturbation d in T_cw <- exp(d) T_cw, translation part first (VertexPose::add's convention);
+ *   Sigma_l      = H_ll^-1 + H_ll^-1 (sum over the landmark's edges e, e' of H_lp,e Sigma_pp[p(e), p(e')] H_pl,e') H_ll^-1,
+ *                H_lp,e = J_l,e^T W_e J_p,e: symmetric 3x3, in window landmark order.  A landmark no edge observes is
+ *                no vertex: nine NaNs.  So is, under degenerate_guard = 1, a rank-deficient landmark (held fixed by
+ *                the solver, it adds nothing to S).
+ *
+ * Deleting the anchor's rows and columns conditions on that pose.  A window without a fixed pose has a gauge freedom:
+ * its S is numerically singular, and anchor (the oldest keyframe, say) is there for it.
+ * The outputs are exactly symmetric, two calls return the same bits, and the call changes nothing a later solve
+ * returns (it reads the solver's state and writes buffers of its own).
+ *
+ * LH_E_STATE: no completed solve of the uploaded window on the handle.  LH_E_BADARG: a null in or out, anchor outside
+ * [-1, n_poses).  LH_E_UNSUPPORTED: n_poses > 64 (the inverse of a banded S is dense), world_size > 1.
+ * LH_E_SINGULAR: no free pose (bad_row 0); a pivot of the Cholesky factor of S[f, f] that is not > 0 (bad_row: its row
+ * of the 6 n_poses), which is what a free gauge gives; degenerate_guard = 0 on a window with rank-deficient landmarks.
+ * On LH_E_SINGULAR no output array is written. */
+typedef struct lh_cov_input {
+    int32_t anchor;        /* pose held in addition to pose_fixed; -1: none */
+} lh_cov_input;
+typedef struct lh_cov_result {
+    double *pose_cov;      /* [n_poses][36] diagonal blocks Sigma_pp[p, p], row-major, or NULL               */
+    double *pose_cov_full; /* [6 n_poses][6 n_poses] row-major, or NULL                                        */
+    double *lm_cov;        /* [n_landmarks][9] window order, or NULL (then no landmark kernel runs)            */
+    int32_t n_free;        /* rows factored (6 x free poses)                                                   */
+    int32_t bad_row;       /* first row whose pivot was not > 0 (LH_E_SINGULAR), else -1                       */
+    double min_pivot, max_pivot;  /* of the factor's L_ii^2: a cheap conditioning signal                       */
+    double time_ms;        /* device time (HIP events), linearisation included, the download excluded          */
+} lh_cov_result;
+int lh_covariance(lh_handle *h, const lh_cov_input *in, lh_cov_result *out);
 
 /* ---- test hooks (not part of the reference interface) ---- */
 /* f64 MFMA accumulator-layout probe: D(16x16) = A(16x4) * B(4x16), device pointers, row-major */

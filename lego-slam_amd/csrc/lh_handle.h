@@ -101,6 +101,18 @@ struct FrontendState {
     HostBuf<uint8_t> s_kfin, s_kfout;
 };
 
+// What lh_covariance keeps between calls (lh_cov_host.cpp): a second set of lh_reset_args holding the last solve's
+// returned state, and everything its linearisation there writes that the solve's own state also holds (controller,
+// step, poses, tables, records, reduced system), so that the handle's solver state is only read
+struct CovState {
+    DevBuf<double> qt_init, ptab_init, lm;     // the snapshot: lh_reset_args' three arrays
+    DevBuf<double> qt, ptab, rec, dxp, rs, maxd;
+    DevBuf<lh_ctrl> ctrl;
+    DevBuf<int32_t> rowmap;
+    DevBuf<double> A, W, full;                 // S[f, f] and its factor, L^-1, Sigma_pp (when it is not downloaded)
+    DevBuf<double> out;                        // the download: the result block, then the arrays asked for
+};
+
 }  // namespace lh
 
 struct lh_handle {
@@ -176,6 +188,8 @@ struct lh_handle {
     DevBuf<uint8_t> d_wflag;     // [2][n_slots] inlier flags of each state buffer's linearisation (k_lin)
     DevBuf<double> d_img;        // [2][LH_IMG_SZ] k_ctrl's LDS system image, staged / committed (prm.img)
     lh::FrontendState fe;
+    lh::CovState cov;
+    bool solved = false;         // a solve of the uploaded window has completed (lh_covariance reads its state)
     lh_ctrl* h_ctrl = nullptr;   // pinned
     int last_chains = -1;        // lh_debug_chains: the last synchronous solve's stop chain
     int last_lskips = -1;        // lh_debug_ladder: its rejections onto a built ladder rung

@@ -615,6 +615,7 @@ int send_arena(lh_handle* h, bool sync) {
 int upload_body(lh_handle* h, const lh_window* w, bool sync) {
     const double t0 = now_ms();
     h->uploaded = false;
+    h->solved = false;
     const lh::Switches sw = lh::read_switches();
     STAGE(wait_staging(h));
     STAGE(send_landmarks(h, w));
@@ -1110,6 +1111,7 @@ const char* lh_strerror(int status) {
         case LH_E_RCCL: return "RCCL / exchange error";
         case LH_E_UNSUPPORTED: return "window outside the supported envelope";
         case LH_E_STATE: return "call out of order";
+        case LH_E_SINGULAR: return "singular system: no free pose, a pivot that is not positive, or rank-deficient landmarks";
         default: return "unknown status";
     }
 }
@@ -1277,8 +1279,11 @@ int lh_upload(lh_handle* h, const lh_window* in) {
 int lh_solve_resident(lh_handle* h, lh_result* out) {
     if (!h) return LH_E_BADARG;
     if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
+    h->solved = false;
     try {
-        return solve_resident_impl(h, out);
+        const int st = solve_resident_impl(h, out);
+        h->solved = st == LH_OK;   // (lh_covariance works on the state this solve returned)
+        return st;
     } catch (...) {
         return LH_E_HIP;
     }

@@ -1,12 +1,13 @@
 // lh_launch.h — the one declaration of every kernel launcher.  The definitions (lh_lin.hip, lh_kernels.hip and its lh_probe.hip, lh_frames.hip,
-// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip, lh_track.hip, lh_keyframe.hip) and the callers (lh_host.cpp, lh_frontend.cpp) all include it: the symbols are extern "C", so only
+// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip, lh_track.hip, lh_keyframe.hip, lh_cov.hip) and the callers (lh_host.cpp, lh_frontend.cpp, lh_cov_host.cpp) all include it: the symbols are extern "C", so only
 // the compiler, seeing a definition beside this declaration, can tell that the two sides disagree.
-// (lh_tri.h, lh_gftt.h, lh_klt.h and lh_track.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.
+// (lh_tri.h, lh_gftt.h, lh_klt.h, lh_track.h and lh_cov.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.
 // lh_keyframe.h holds its kernels' arguments alone, and no HIP type either.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "lh_common.h"
+#include "lh_cov.h"
 #include "lh_gftt.h"
 #include "lh_keyframe.h"
 #include "lh_klt.h"
@@ -70,4 +71,7 @@ hipError_t lh_launch_track_guess(hipStream_t st, const lh_track_args* a);
 hipError_t lh_launch_track_pack(hipStream_t st, const lh_track_args* a);
 hipError_t lh_launch_kf_assemble(hipStream_t st, const lh_kf_args* a);
 hipError_t lh_launch_kf_finish(hipStream_t st, const lh_kf_args* a);
+hipError_t lh_launch_cov_snapshot(hipStream_t st, const lh_cov_snap_args* a);
+hipError_t lh_launch_cov_pose(hipStream_t st, const lh_cov_args* a);
+hipError_t lh_launch_cov_lm(hipStream_t st, const lh_cov_lm_args* a, lh_params prm);
 }

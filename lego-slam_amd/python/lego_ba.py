@@ -120,7 +120,7 @@ def config_window(name, seed=0, **kw):
 # solver C ABI (include/lego_ba.h)
 # --------------------------------------------------------------------------
 
-LH_OK, LH_E_EMPTY, LH_E_BADARG, LH_E_HIP, LH_E_RCCL, LH_E_UNSUPPORTED, LH_E_STATE = range(7)
+LH_OK, LH_E_EMPTY, LH_E_BADARG, LH_E_HIP, LH_E_RCCL, LH_E_UNSUPPORTED, LH_E_STATE, LH_E_SINGULAR = range(8)
 LH_ABI_VERSION = 5
 LH_SOLVER_LDLT, LH_SOLVER_PCG = 0, 1
 LH_PREC_FP64, LH_PREC_FP32_RESID = 0, 1
@@ -262,6 +262,15 @@ class LhKeyframeResult(C.Structure):
                 ("n_right", C.c_int32), ("n_accepted", C.c_int32), ("time_ms", C.c_double)]
 
 
+class LhCovInput(C.Structure):
+    _fields_ = [("anchor", C.c_int32)]
+
+
+class LhCovResult(C.Structure):
+    _fields_ = [("pose_cov", C.c_void_p), ("pose_cov_full", C.c_void_p), ("lm_cov", C.c_void_p), ("n_free", C.c_int32),
+                ("bad_row", C.c_int32), ("min_pivot", C.c_double), ("max_pivot", C.c_double), ("time_ms", C.c_double)]
+
+
 class LhDetectInput(C.Structure):
     _fields_ = [
         ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int64), ("img", C.c_void_p), ("mask", C.c_void_p),
@@ -291,7 +300,7 @@ ABI_SYMBOLS = [
     "lh_create", "lh_destroy", "lh_solve", "lh_upload", "lh_solve_resident",
     "lh_kernel_stats_get", "lh_kernel_stats_reset", "lh_classify_outliers", "lh_set_profiling",
     "lh_estimate_pose", "lh_lk_track", "lh_triangulate", "lh_stereo_landmarks", "lh_detect_features",
-    "lh_klt_track", "lh_klt_stereo_landmarks", "lh_track_frame", "lh_insert_keyframe",
+    "lh_klt_track", "lh_klt_stereo_landmarks", "lh_track_frame", "lh_insert_keyframe", "lh_covariance",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
     "lh_debug_batch", "lh_debug_reduced_system",
@@ -336,6 +345,8 @@ def ba_lib():
             lib.lh_track_frame.argtypes = [C.c_void_p, C.POINTER(LhTrackInput), C.POINTER(LhTrackResult)]
         if hasattr(lib, "lh_insert_keyframe"):
             lib.lh_insert_keyframe.argtypes = [C.c_void_p, C.POINTER(LhKeyframeInput), C.POINTER(LhKeyframeResult)]
+        if hasattr(lib, "lh_covariance"):
+            lib.lh_covariance.argtypes = [C.c_void_p, C.POINTER(LhCovInput), C.POINTER(LhCovResult)]
         lib.lh_classify_outliers.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lh_debug_event_floor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -432,6 +443,7 @@ class Solver:
         _check(lib.lh_create(C.byref(h), C.byref(self.opts)), "lh_create")
         self.h = h
         self._win = None
+        self._dims = (0, 0)   # poses and landmarks of the window the handle holds (covariance sizes its arrays by them)
 
     def close(self):
         if self.h:
@@ -484,6 +496,28 @@ class Solver:
             out["outlier_th"], out["n_inlier"], out["n_outlier"] = r.outlier_th, r.n_inlier, r.n_outlier
         return out
 
+    def covariance(self, anchor=-1, full=False, landmarks=False, out=None):
+        """lh_covariance of the window last solved on this handle: the marginal covariance of the poses (left
+        perturbation, translation first; held poses zero) and, with landmarks=True, of the landmarks.  anchor: a pose held
+        in addition to the fixed ones (-1: none).  Returns pose_cov [P, 6, 6], pose_cov_full [6P, 6P] (full=True),
+        lm_cov [L, 3, 3] (landmarks=True), n_free, bad_row, min_pivot, max_pivot, time_ms.  A singular system raises
+        LhError(LH_E_SINGULAR) with the result so far in its `result` attribute (bad_row; no array is written).
+        out: a dict of preallocated arrays to write (pose_cov, pose_cov_full, lm_cov) instead of fresh ones."""
+        P, L = self._dims
+        out = {} if out is None else out
+        a = dict(pose_cov=out.get("pose_cov", np.zeros((P, 6, 6))),
+                 pose_cov_full=out.get("pose_cov_full", np.zeros((6 * P, 6 * P))) if full else None,
+                 lm_cov=out.get("lm_cov", np.zeros((L, 3, 3))) if landmarks else None)
+        i, r = LhCovInput(int(anchor)), LhCovResult()
+        r.pose_cov, r.pose_cov_full, r.lm_cov = _ptr(a["pose_cov"]), _ptr(a["pose_cov_full"]), _ptr(a["lm_cov"])
+        st = ba_lib().lh_covariance(self.h, C.byref(i), C.byref(r))
+        a.update(n_free=r.n_free, bad_row=r.bad_row, min_pivot=r.min_pivot, max_pivot=r.max_pivot, time_ms=r.time_ms)
+        if st != LH_OK:
+            e = LhError(st, "lh_covariance")
+            e.result = a
+            raise e
+        return a
+
     def solve(self, w, trace_cap=64, reuse=None, outlier_chi2_th=None, want_edges=True):
         """lh_solve on host buffers.  reuse: a previous call's result dict whose output arrays are
         written again (a caller's persistent buffers) instead of freshly allocated ones.
@@ -492,11 +526,13 @@ class Solver:
         ref = _WindowRef(w)
         r, out = self._result(ref.s.n_poses, ref.s.n_landmarks, ref.s.n_obs, trace_cap, want_edges=want_edges,
                               reuse=reuse, outlier_chi2_th=outlier_chi2_th)
+        self._dims = (ref.s.n_poses, ref.s.n_landmarks)
         _check(ba_lib().lh_solve(self.h, C.byref(ref.s), C.byref(r)), "lh_solve")
         return self._finish(r, out)
 
     def upload(self, w):
         self._win = _WindowRef(w)
+        self._dims = (self._win.s.n_poses, self._win.s.n_landmarks)
         _check(ba_lib().lh_upload(self.h, C.byref(self._win.s)), "lh_upload")
 
     _SCALARS = ("iterations", "trials", "accepted", "chi2_initial", "chi2_final", "lambda_final", "time_ms",
