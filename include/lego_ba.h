@@ -704,6 +704,10 @@ int lh_debug_pcg_probe(const double* S, const double* b, int n, double tol, int 
 int lh_debug_event_floor(lh_handle *h, double *ms);
 /* per-phase wave-cycle totals of a -DLH_STAMPS diagnostic build (all zero in the product build) */
 int lh_debug_stamps(unsigned long long *out, int n, int reset);
+/* k_lin's waves in a -DLH_STAMPS diagnostic build (all zero in the product build): 8 words per (workgroup, wave) of
+   the last full trial launch, workgroup-major: [0] HW_ID | XCC_ID << 32 | 1 << 40, [1] the clock at the wave's entry
+   to its sub-batch loop, [2 + r] at the end of its r-th sub-batch.  Up to 16384 words; cleared by the read. */
+int lh_debug_lin_stamps(unsigned long long *out, int n);
 /* k_lin's duration per LM trial, measured after a solve: the trial-mode k_lin launch(es) replayed
    reps times back to back between two HIP events on the handle's stream (ms per replay).  The
    replay rewrites the candidate buffers and the per-edge chi2: read the solve's outputs first. */
@@ -715,6 +719,10 @@ int lh_debug_comm_count(lh_handle *h, int64_t *n);
    bit 8: k_ctrl_b's back substitution holds one row per lane (every row's envelope within 56 rows);
    bit 9: some k_ctrl_b step needs more than 11 unit waves, so its stream loaders take units too */
 int lh_debug_controller(lh_handle *h, int *which);
+/* k_lin's shape on the uploaded window: waves per workgroup (4, or 8: one workgroup per compute unit, the planner's
+   choice for a window that fills the GPU; LH_NO_LIN_WG8=1 keeps 4), the window's chunks, and the landmarks-per-chunk
+   bound they were cut with */
+int lh_debug_lin_shape(lh_handle *h, int *waves, int *chunks, int *chunk_landmarks);
 /* the LM chains (k_lin, k_reduce, exchange, controller) the last solve decided past the initial
    linearisation: its trials, plus one re-linearisation per evaluate-only trial accepted outside the
    final iteration (a trial after a rejection only evaluates).  Solves that return arrays only. */

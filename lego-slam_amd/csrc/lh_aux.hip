@@ -260,4 +260,19 @@ hipError_t lh_read_stamps(unsigned long long* out, int n, int reset) {
 #endif
 }
 
+// k_lin's per-wave records of the -DLH_STAMPS build (lh_dev.h lh_lin_stamps; zeros otherwise), cleared after the read
+hipError_t lh_read_lin_stamps(unsigned long long* out, int n) {
+#ifdef LH_STAMPS
+    static unsigned long long z[LH_LSTAMP_N];
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(lh_lin_stamps),
+                                       sizeof(unsigned long long) * (n < LH_LSTAMP_N ? n : LH_LSTAMP_N));
+    if (e != hipSuccess) return e;
+    for (int i = LH_LSTAMP_N; i < n; ++i) out[i] = 0;
+    return hipMemcpyToSymbol(HIP_SYMBOL(lh_lin_stamps), z, sizeof(z));
+#else
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    return hipSuccess;
+#endif
+}
+
 }  // extern "C"

@@ -21,6 +21,7 @@
 #define LH_SB_LM 8            // landmarks per sub-batch (one wave)
 #define LH_SB_OBS 64          // observations per sub-batch (one per lane)
 #define LH_WAVES 4            // waves per k_lin workgroup
+#define LH_WAVES_WG8 8        // ... of the one-workgroup-per-CU shape (T <= 3; the planner's choice, lh::Plan::lin_waves)
 #define LH_TASKS 33           // per-pose values a sub-batch emits: Hpp(21) bp(6) bsd(6)
 #define LH_MAX_CAMS 4
 #define LH_TRACE 64

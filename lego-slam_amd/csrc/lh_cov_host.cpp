@@ -65,7 +65,7 @@ int covariance_impl(lh_handle* h, const lh_cov_input* in, lh_cov_result* out) {
     for (int T = 1; T <= LH_TMAX; ++T) {   // as the solver's initial linearisation (lh_host.cpp launch_lin)
         const int c0 = h->plan.tgroup_begin[T], c1 = h->plan.tgroup_begin[T + 1];
         if (c1 == c0 && !(writer && T == LH_TMAX)) continue;
-        HIPCHK(lh_launch_lin(T, 0, c1 - c0, c0, s, h->d_chunks.p, h->d_sbs.p, h->d_uv.p, h->d_meta.p, cv.rec.p, cv.ptab.p,
+        HIPCHK(lh_launch_lin(T, h->plan.lin_waves, 0, c1 - c0, c0, s, h->d_chunks.p, h->d_sbs.p, h->d_uv.p, h->d_meta.p, cv.rec.p, cv.ptab.p,
                              h->d_ext.p, cv.ctrl.p, cv.dxp.p, h->d_rho.p, h->d_rows.p, h->d_csc.p, h->d_items.p,
                              h->d_wflag.p, (long)h->n_slots, h->prm, h->n_rec, h->d_fixed.p, cv.qt.p, writer, rst));
         writer = 0;

@@ -35,6 +35,28 @@ __device__ unsigned long long lh_stamps[256];   // [64, 128): k_ctrl's LDL^T ste
             for (int i_ = 0; i_ < (cnt); ++i_)                                     \
                 if (sacc_[((base) + i_) % 24]) atomicAdd(&lh_stamps[(base) + i_], sacc_[((base) + i_) % 24]); \
     } while (0)
+// k_lin's waves, one record of LH_LSTAMP_REC words per (workgroup, wave) of the last full trial launch: [0] the
+// wave's HW_ID word | its XCC_ID << 32 | 1 << 40, [1] s_memtime when it enters the sub-batch loop, [2 + r] s_memtime
+// at the end of its r-th sub-batch (r < 6).  Which waves share a SIMD, and which of them run the extra sub-batch
+// beside another such wave or alone (scripts/lin_wave_stamps.py).
+#define LH_LSTAMP_REC 8
+#define LH_LSTAMP_N 16384
+__device__ unsigned long long lh_lin_stamps[LH_LSTAMP_N];
+#define LSTAMP_DECL(on, blk, nw, wave)                                                              \
+    unsigned long long* lst_ = nullptr;                                                             \
+    int lround_ = 0;                                                                                \
+    if ((on) && ((blk) * (nw) + (wave) + 1) * LH_LSTAMP_REC <= LH_LSTAMP_N && (threadIdx.x & 63) == 0) { \
+        lst_ = lh_lin_stamps + ((blk) * (nw) + (wave)) * LH_LSTAMP_REC;                             \
+        for (int i_ = 2; i_ < LH_LSTAMP_REC; ++i_) lst_[i_] = 0ull;                                 \
+        lst_[0] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4) |                             \
+                  ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32) | (1ull << 40); \
+        lst_[1] = __builtin_amdgcn_s_memtime();                                                     \
+    }
+#define LSTAMP_ROUND()                                                                              \
+    do {                                                                                            \
+        if (lst_ && lround_ < LH_LSTAMP_REC - 2) lst_[2 + lround_] = __builtin_amdgcn_s_memtime();  \
+        ++lround_;                                                                                  \
+    } while (0)
 // k_ctrl wall-clock stamps: thread 0 (wave 0, the critical chain) adds s_memtime at each
 // barrier-aligned phase boundary of every live launch into lh_stamps[32 + i]; consecutive sums
 // difference to per-phase latency.  [61] live launches, [62]/[63] s_memrealtime at start / end.
@@ -66,6 +88,8 @@ __device__ unsigned long long lh_stamps[256];   // [64, 128): k_ctrl's LDL^T ste
 #define STAMP_DECL
 #define STAMP(i)
 #define STAMP_FLUSH(base, cnt)
+#define LSTAMP_DECL(on, blk, nw, wave)
+#define LSTAMP_ROUND()
 #define CSTAMP(i)
 #define CSTAMP_START
 #define CSTAMP_LIVE()

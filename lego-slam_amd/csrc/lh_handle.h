@@ -122,6 +122,7 @@ struct lh_handle {
     lh_options opt;
     int device = 0;
     int lds_limit = 160 * 1024;   // hipDeviceAttributeMaxSharedMemoryPerBlock of the device
+    int n_cu = 256;               // hipDeviceAttributeMultiprocessorCount of the device (the planner's k_lin shape)
     hipStream_t stream = nullptr;
     lh::Transport transport = lh::TR_NONE;
     ncclComm_t comm = nullptr;    // TR_RCCL's communicator

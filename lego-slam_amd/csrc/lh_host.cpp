@@ -301,10 +301,14 @@ int send_landmarks(lh_handle* h, const lh_window* w) {
     return LH_OK;
 }
 
-int plan_window(lh_handle* h, const lh_window* w) {
+int plan_window(lh_handle* h, const lh_window* w, const lh::Switches& sw) {
     lh::PlanCfg cfg;
     cfg.chunk_lm = h->opt.chunk_landmarks;
     cfg.rank_invariant_pairs = h->opt.world_size > 1;
+    cfg.n_cu = h->n_cu;
+    cfg.lin_smem = lh_lin_smem;
+    cfg.lds_limit = (size_t)h->lds_limit;
+    lh::apply_switches(cfg, sw);
     const int st = lh::plan_structure(w, cfg, h->opt.world_size > 1, h->plan, h->pool);
     if (st != LH_OK) {
         HIPCHK(hipEventRecord(h->ev_staging, h->stream));
@@ -321,7 +325,7 @@ int rank_local_limits(lh_handle* h) {
     if ((size_t)2 * pl.n_rec * LH_REC * sizeof(double) > (size_t)INT32_MAX) return LH_E_UNSUPPORTED;
     // a chunk window must fit one CU's LDS
     for (int T = 1; T <= LH_TMAX; ++T)
-        if (pl.tgroup_begin[T + 1] > pl.tgroup_begin[T] && lh_lin_smem(T, pl.ncam) > (size_t)h->lds_limit)
+        if (pl.tgroup_begin[T + 1] > pl.tgroup_begin[T] && lh_lin_smem(T, pl.ncam, pl.lin_waves) > (size_t)h->lds_limit)
             return LH_E_UNSUPPORTED;
     return LH_OK;
 }
@@ -503,6 +507,7 @@ int configure(lh_handle* h, const std::vector<int>& pf, const lh::Switches& sw) 
     lh::SolveIn in;
     in.P = h->P;
     in.n_brow_ent = h->plan.brow_ent.size();
+    in.lin_waves = h->plan.lin_waves;
     in.pf = pf.data();
     in.linear_solver = h->opt.linear_solver;
     in.max_trials = h->opt.max_trials;
@@ -619,7 +624,7 @@ int upload_body(lh_handle* h, const lh_window* w, bool sync) {
     const lh::Switches sw = lh::read_switches();
     STAGE(wait_staging(h));
     STAGE(send_landmarks(h, w));
-    STAGE(plan_window(h, w));
+    STAGE(plan_window(h, w, sw));
     std::vector<int> pf = lh::plan_envelope(h->plan);   // this rank's; the collective below unites the ranks'
     STAGE(rank_local_limits(h));
     STAGE(bind_arena(h, lh::band_possible(h->plan.P, h->opt.linear_solver, sw)));
@@ -665,7 +670,7 @@ int launch_lin(lh_handle* h, int trial) {
         const int c0 = h->plan.tgroup_begin[T], c1 = h->plan.tgroup_begin[T + 1];
         const bool last = T == LH_TMAX;
         if (c1 == c0 && !(writer && last)) continue;
-        HIPCHK(lh_launch_lin(T, trial, c1 - c0, c0, s, h->d_chunks.p, h->d_sbs.p, h->d_uv.p, h->d_meta.p, h->d_rec.p,
+        HIPCHK(lh_launch_lin(T, h->plan.lin_waves, trial, c1 - c0, c0, s, h->d_chunks.p, h->d_sbs.p, h->d_uv.p, h->d_meta.p, h->d_rec.p,
                              h->d_ptab.p, h->d_ext.p, h->d_ctrl.p, h->d_dxp.p, h->d_rho.p, h->d_rows.p,
                              h->d_csc.p, h->d_items.p, h->d_wflag.p, (long)h->n_slots, h->prm, h->n_rec,
                              h->d_fixed.p, h->d_qt.p, writer, rst));
@@ -1191,6 +1196,8 @@ int lh_create(lh_handle** hp, const lh_options* opt) {
     int lds = 0;
     if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && lds > 0)
         h->lds_limit = lds;
+    int ncu = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) h->n_cu = ncu;
     if (lh_prepare_lin(h->lds_limit) != hipSuccess) { delete h; return LH_E_HIP; }
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return LH_E_HIP; }
     if (hipHostMalloc((void**)&h->h_ctrl, sizeof(lh_ctrl), hipHostMallocDefault) != hipSuccess ||
@@ -1357,6 +1364,13 @@ int lh_debug_stamps(unsigned long long* out, int n, int reset) {
     return lh_read_stamps(out, n, reset) == hipSuccess ? LH_OK : LH_E_HIP;
 }
 
+// diagnostic hook: k_lin's per-wave records of the -DLH_STAMPS build (zeros otherwise)
+int lh_debug_lin_stamps(unsigned long long* out, int n) {
+    if (!out || n < 0) return LH_E_BADARG;
+    if (hipDeviceSynchronize() != hipSuccess) return LH_E_HIP;
+    return lh_read_lin_stamps(out, n) == hipSuccess ? LH_OK : LH_E_HIP;
+}
+
 // test hook: k_ctrl's reduced-system solve on a dense symmetric S, device pointers
 // (n > LH_NPAD: k_ctrl_g's global-memory solve, the windows past LH_PMAX poses)
 int lh_debug_ldlt_probe(const double* S, const double* b, int n, double* x) {
@@ -1486,6 +1500,15 @@ int lh_debug_controller(lh_handle* h, int* which) {
     if (!h->uploaded) return LH_E_STATE;
     // lh_ctrl_kind | bit 8: k_ctrl_b's one-row-per-lane back substitution | bit 9: its stream loaders take units
     *which = h->cfg.debug_word();
+    return LH_OK;
+}
+
+int lh_debug_lin_shape(lh_handle* h, int* waves, int* chunks, int* chunk_landmarks) {
+    if (!h || !waves || !chunks || !chunk_landmarks) return LH_E_BADARG;
+    if (!h->uploaded) return LH_E_STATE;
+    *waves = h->cfg.lin_waves;
+    *chunks = h->plan.n_chunks;
+    *chunk_landmarks = h->plan.chunk_lm;
     return LH_OK;
 }
 

@@ -17,7 +17,7 @@
 
 extern "C" {
 hipError_t lh_prepare_lin(int lds_limit);
-size_t lh_lin_smem(int T, int ncam);
+size_t lh_lin_smem(int T, int ncam, int nw);
 hipError_t lh_launch_nop(hipStream_t st);
 hipError_t lh_launch_outliers(hipStream_t st, const double* rho, const int32_t* obs_perm, long nslots, long n_obs,
                               double th0, unsigned* part, uint8_t* flags);
@@ -27,7 +27,7 @@ hipError_t lh_launch_outlier_counts(hipStream_t st, const double* rho, const int
                                     double th0, unsigned* part, double* tot);
 hipError_t lh_launch_outlier_flags(hipStream_t st, const double* rho, const int32_t* obs_perm, long nslots, long n_obs,
                                    double th0, const double* gtot, uint8_t* flags);
-hipError_t lh_launch_lin(int T, int trial, int nchunks, int chunk_base, hipStream_t st, const lh_chunk* chunks,
+hipError_t lh_launch_lin(int T, int nw, int trial, int nchunks, int chunk_base, hipStream_t st, const lh_chunk* chunks,
                          const lh_subbatch* sbs, const float* obs_uv, const uint32_t* obs_meta, double* rec,
                          double* ptab, const double* ext, const lh_ctrl* ctrl, const double* dxp,
                          double* edge_rho, double* rows, double* csc, const uint32_t* crow, uint8_t* wflag,
@@ -51,6 +51,7 @@ hipError_t lh_launch_ldlt_probe(const double* S, const double* b, int n, double*
                                 int* iters);
 hipError_t lh_launch_mfma_probe(const double* A, const double* B, double* D);
 hipError_t lh_read_stamps(unsigned long long* out, int n, int reset);
+hipError_t lh_read_lin_stamps(unsigned long long* out, int n);
 hipError_t lh_launch_frames(hipStream_t st, int n_frames, const int64_t* obs_ptr, const double* pose_in,
                             const double* pts, const double* uv, const uint8_t* flag_in, lh_params prm, double* res,
                             double* pose_out, uint8_t* flag_out, double* rchi2_out, int32_t* iters_out,

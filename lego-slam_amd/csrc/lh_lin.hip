@@ -151,13 +151,14 @@ __device__ __forceinline__ void lin_backsub(const double* __restrict__ pt, const
 // pose of slot i % U, from the committed pose pm (slot's pose cpose[slot]) and the rung's step (LDS wd + 6 U r),
 // staged in LDS cand; then item j < gn U ncam builds the table of (rung, slot, camera) into LDS tabs + per_tab r,
 // as k_lin's own candidate build does.  LDS operands as offsets into the dynamic LDS; out of line, so that its
-// registers are not the trial path's.
+// registers are not the trial path's.  NTH: the workgroup's threads.
+template <int NTH>
 __device__ __attribute__((noinline)) void lin_cand_batch(const double* __restrict__ pm, const uint16_t* __restrict__ cpose,
                                                          int pmax1, int U, int ncam, int gn, int o_wd, int o_cand,
                                                          int o_tabs, int per_tab, int o_wext) {
     extern __shared__ __attribute__((aligned(16))) double dsm[];
     const int tid = threadIdx.x;
-    for (int i = tid; i < gn * U; i += 256) {
+    for (int i = tid; i < gn * U; i += NTH) {
         const int r = i / U, sl = i - r * U;
         const uint32_t pp = min((uint32_t)cpose[sl], (uint32_t)pmax1);
         double pmc[12], To[12];
@@ -168,7 +169,7 @@ __device__ __attribute__((noinline)) void lin_cand_batch(const double* __restric
         for (int k = 0; k < 12; ++k) dsm[o_cand + 12 * i + k] = To[k];
     }
     lds_barrier();
-    for (int i = tid; i < gn * U * ncam; i += 256) {
+    for (int i = tid; i < gn * U * ncam; i += NTH) {
         const int r = i / (U * ncam), j = i - r * U * ncam, sl = j / ncam, c = j - sl * ncam;
         double To[12];
 #pragma unroll
@@ -180,8 +181,13 @@ __device__ __attribute__((noinline)) void lin_cand_batch(const double* __restric
 #ifndef LH_LIN_OCC
 #define LH_LIN_OCC 2   // k_lin<T <= 3> workgroups per CU the registers are budgeted for
 #endif
-template <int T, bool TRIAL, bool F32>
-__global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
+// NW: the workgroup's waves.  4: up to LH_LIN_OCC workgroups share a CU.  8 (T <= 3 only, the planner's choice for a
+// window that fills the GPU, lh_plan.cpp): one workgroup holds a CU's whole share, its 8 waves at k_lin's ~210 VGPRs
+// fill the register file, so no second workgroup joins and waves w and w + 4 are the two of one SIMD (the HW_ID
+// period DESIGN.md 2.2 records).  Sub-batch i of the chunk runs on wave i mod NW, so the waves that run one
+// sub-batch more than the others (the first n mod NW) sit on distinct SIMDs whenever n mod 8 <= 4.
+template <int T, bool TRIAL, bool F32, int NW>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : ((T <= 3) ? LH_LIN_OCC : 1)) void k_lin(
     const lh_chunk* __restrict__ chunks, const lh_subbatch* __restrict__ sbs, const float* __restrict__ obs_uv,
     const uint32_t* __restrict__ obs_meta, double* __restrict__ rec, double* __restrict__ pose_tab,
     const double* __restrict__ ext, const lh_ctrl* __restrict__ ctrl, const double* __restrict__ dxp,
@@ -190,6 +196,8 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
     lh_params prm, int nrec, const uint64_t* __restrict__ fixed_bits, int chunk_base,
     double* __restrict__ pose_mat, int writer, lh_reset_args rst) {
     using Cfg = LinCfg<T>;
+    static_assert(NW == 4 || (NW == 8 && T <= 3), "4 waves, or 8 for T <= 3");
+    constexpr int NTH = 64 * NW;   // threads
     extern __shared__ __attribute__((aligned(16))) double dsm[];
 
     // The prologue's global loads go out in two dependent rounds: (1) the controller words and the
@@ -218,22 +226,22 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         // (ctrl and dxp are read-only to every trial launch; in this launch no other block reads them, and
         // the controller words written here are read by the later kernels of the chain)
         int* c = reinterpret_cast<int*>(const_cast<lh_ctrl*>(ctrl));
-        for (int i = threadIdx.x; i < (int)(sizeof(lh_ctrl) / sizeof(int)); i += 256) c[i] = 0;   // cur = 0
-        for (int i = threadIdx.x; i < rst.nqt; i += 256) pose_mat[i] = rst.qt_init[i];
-        for (int i = threadIdx.x; i < rst.nptab; i += 256) pose_tab[i] = rst.ptab_init[i];
-        for (int i = threadIdx.x; i < rst.ndxp; i += 256) const_cast<double*>(dxp)[i] = 0.0;
+        for (int i = threadIdx.x; i < (int)(sizeof(lh_ctrl) / sizeof(int)); i += NTH) c[i] = 0;   // cur = 0
+        for (int i = threadIdx.x; i < rst.nqt; i += NTH) pose_mat[i] = rst.qt_init[i];
+        for (int i = threadIdx.x; i < rst.nptab; i += NTH) pose_tab[i] = rst.ptab_init[i];
+        for (int i = threadIdx.x; i < rst.ndxp; i += NTH) const_cast<double*>(dxp)[i] = 0.0;
         return;
     }
     if (TRIAL && writer && blockIdx.x == 0) {
         if (done || nbatch > 1) return;   // (a batch writes no candidate: its accepted rung is re-run in full)
         const int P = prm.P, nc = prm.ncam, cnd = 1 - cur;
         if (relin) {
-            for (int i = threadIdx.x; i < P * 12; i += 256) pose_mat[(size_t)cnd * P * 12 + i] = pose_mat[(size_t)cur * P * 12 + i];
-            for (int i = threadIdx.x; i < P * nc * LH_PT; i += 256)
+            for (int i = threadIdx.x; i < P * 12; i += NTH) pose_mat[(size_t)cnd * P * 12 + i] = pose_mat[(size_t)cur * P * 12 + i];
+            for (int i = threadIdx.x; i < P * nc * LH_PT; i += NTH)
                 pose_tab[(size_t)cnd * P * nc * LH_PT + i] = pose_tab[(size_t)cur * P * nc * LH_PT + i];
             return;
         }
-        for (int p = threadIdx.x; p < P; p += 256) {
+        for (int p = threadIdx.x; p < P; p += NTH) {
             double Tc[12], To[12];
 #pragma unroll
             for (int i = 0; i < 12; ++i) Tc[i] = pose_mat[(size_t)cur * P * 12 + p * 12 + i];
@@ -265,16 +273,17 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
     double* scr = dsm + wave * Cfg::SCR;
     // the chunk's window, LDS-resident: committed and candidate pose tables per (slot, camera),
     // the pending pose step per slot, the camera extrinsics
-    double* wt_c = dsm + LH_WAVES * Cfg::SCR;
+    double* wt_c = dsm + NW * Cfg::SCR;
     double* wt_n = wt_c + Cfg::UMAX * ncam * LH_PT_LDS;     // a chunk of T tiles has U <= UMAX poses
     double* wdx = wt_n + Cfg::UMAX * ncam * LH_PT_LDS;
     double* wext = wdx + Cfg::UMAX * 6;
     // after the pair-row map: the flag raised when wave 3 has built the candidate tables
     int* cflag = reinterpret_cast<int*>(wext + ncam * LH_EXT + (Cfg::UMAX * (Cfg::UMAX + 1) / 2 + 1) / 2);
     double pmc[12];
-    // the wave that builds the candidate pose tables: 3 or 2 by block parity, so the two chunks sharing a
-    // CU build them on different SIMDs (measured 37.7 -> 37.5 us per k_lin against wave 3 in both)
-    const int cwave = LH_WAVES - 1 - (blockIdx.x & 1);
+    // the wave that builds the candidate pose tables.  4 waves: 3 or 2 by block parity, so the two chunks sharing a
+    // CU build them on different SIMDs (measured 37.7 -> 37.5 us per k_lin against wave 3 in both).  8 waves: the
+    // last one, which never runs more sub-batches than another wave.
+    const int cwave = NW - 1 - (NW == 4 ? (blockIdx.x & 1) : 0);
 
     const double2* __restrict__ rc2 = reinterpret_cast<const double2*>(rec + (size_t)cur * nrec * LH_REC);
     // piece lane & 7 of sub-batch sbx's record (lane >> 3); the initial linearisation reads only X, from the window
@@ -336,7 +345,7 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         // branch, and the wait at its join serialises the rounds again); only the LDS writes are guarded.
         static_assert(6 * Cfg::UMAX <= 256 && Cfg::UMAX * (Cfg::UMAX + 1) / 2 <= 256 && 4 * LH_EXT <= 256,
                       "one element per thread");
-        constexpr int NTAB = (Cfg::UMAX * 4 * LH_PT + 255) / 256;   // ncam <= 4
+        constexpr int NTAB = (Cfg::UMAX * 4 * LH_PT + NTH - 1) / NTH;   // ncam <= 4
         const int per = ncam * LH_PT, ne = U * per, nrow = U * (U + 1) / 2;
         const int umax1 = max(U - 1, 0);
         const uint32_t pmax1 = (uint32_t)(prm.P - 1);
@@ -344,7 +353,7 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         uint32_t tp[NTAB];
 #pragma unroll
         for (int k = 0; k < NTAB; ++k) {
-            const int i = tid + 256 * k;
+            const int i = tid + NTH * k;
             tsl[k] = min(i / per, umax1);
             tp[k] = min((uint32_t)cpose[tsl[k]], pmax1);
         }
@@ -356,7 +365,7 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         double tc[NTAB], tn[NTAB];
 #pragma unroll
         for (int k = 0; k < NTAB; ++k) {
-            const int i = tid + 256 * k;
+            const int i = tid + NTH * k;
             const size_t g = (size_t)tp[k] * per + min(max(i - tsl[k] * per, 0), per - 1);
             tc[k] = pose_tab[(size_t)cur * PT + g];
             tn[k] = TRIAL ? 0.0 : rst.ptab_init[(size_t)cand * PT + g];   // a trial builds its candidate tables
@@ -369,7 +378,7 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         const double dv = TRIAL ? dxp[6 * dp + (tid - 6 * (tid / 6))] : 0.0;
 #pragma unroll
         for (int k = 0; k < NTAB; ++k) {
-            const int i = tid + 256 * k;
+            const int i = tid + NTH * k;
             if (i < ne) {
                 const int r = i - tsl[k] * per, ent = r / LH_PT;
                 const int l = (tsl[k] * ncam + ent) * LH_PT_LDS + (r - ent * LH_PT);
@@ -393,22 +402,22 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         //      once, then each rung's step is applied and its candidate evaluated.  Each lane's chi2 and scale sums
         //      per rung stay in LDS (the same per-lane order as the single-trial path).  Nothing else is written:
         //      k_reduce decides the rungs in order, and the next chain re-runs an accepted rung as a full trial.
-        //      LDS: the trial path's wave scratch [0, 4 SCR), free here: record stages, rung lambdas, the combine's
+        //      LDS: the trial path's wave scratch [0, NW SCR), free here: record stages, rung lambdas, the combine's
         //      wave totals, then per rung of a group: the lanes' sums, candidate tables, step, candidate poses. ----
         double* stg = dsm + wave * (8 * LH_REC_LDS);               // this wave's landmark-record stage
-        double* lam_l = dsm + LH_WAVES * 8 * LH_REC_LDS;           // [LH_LAD] the rungs' lambdas
-        double* wtot = lam_l + LH_LAD;                             // [LH_LAD][LH_WAVES][2] wave totals
-        double* gbase = wtot + LH_LAD * LH_WAVES * 2;
+        double* lam_l = dsm + NW * 8 * LH_REC_LDS;           // [LH_LAD] the rungs' lambdas
+        double* wtot = lam_l + LH_LAD;                             // [LH_LAD][NW][2] wave totals
+        double* gbase = wtot + LH_LAD * NW * 2;
         const int per_tab = U * ncam * LH_PT_LDS;
-        const int per_rung = 2 * LH_WAVES * 64 + per_tab + 6 * U + 12 * U;
-        const int avail = LH_WAVES * Cfg::SCR - (int)(gbase - dsm);
-        static_assert(LH_WAVES * Cfg::SCR - (LH_WAVES * 8 * LH_REC_LDS + LH_LAD + LH_LAD * LH_WAVES * 2) >=
-                          2 * LH_WAVES * 64 + Cfg::UMAX * 4 * LH_PT_LDS + 18 * Cfg::UMAX,
+        const int per_rung = 2 * NW * 64 + per_tab + 6 * U + 12 * U;
+        const int avail = NW * Cfg::SCR - (int)(gbase - dsm);
+        static_assert(NW * Cfg::SCR - (NW * 8 * LH_REC_LDS + LH_LAD + LH_LAD * NW * 2) >=
+                          2 * NW * 64 + Cfg::UMAX * 4 * LH_PT_LDS + 18 * Cfg::UMAX,
                       "a batch group of one rung (4 cameras) fits the wave scratch");
         const int G = max(1, min(nbatch, avail / per_rung));      // rungs per group
-        double* acc_c = gbase;                                     // [G][LH_WAVES][64] chi2 per lane
-        double* acc_s = acc_c + G * LH_WAVES * 64;                 // [G][LH_WAVES][64] gain scale per lane
-        double* tabs = acc_s + G * LH_WAVES * 64;                  // [G][per_tab] candidate tables
+        double* acc_c = gbase;                                     // [G][NW][64] chi2 per lane
+        double* acc_s = acc_c + G * NW * 64;                       // [G][NW][64] gain scale per lane
+        double* tabs = acc_s + G * NW * 64;                        // [G][per_tab] candidate tables
         double* wd = tabs + G * per_tab;                           // [G][6 U] steps
         double* cand = wd + G * 6 * U;                             // [G][U][12] candidate poses
         if (tid == 0) {   // rung r's lambda: r more rejections' updates (ctrl_lm_step, ladder_read's order)
@@ -424,16 +433,16 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         for (int g0 = 0; g0 < nbatch; g0 += G) {
             const int gn = min(G, nbatch - g0);
             lds_barrier();   // (the previous group's combine is done with the LDS)
-            for (int i = tid; i < gn * 6 * U; i += 256) {
+            for (int i = tid; i < gn * 6 * U; i += NTH) {
                 const int r = i / (6 * U), k = i - r * 6 * U;
                 wd[i] = dxp[(size_t)(g0 + r) * prm.n + 6 * (size_t)min((uint32_t)cpose[k / 6], (uint32_t)(prm.P - 1)) + k % 6];
             }
-            for (int i = tid; i < gn * LH_WAVES * 64; i += 256) { acc_c[i] = 0.0; acc_s[i] = 0.0; }
+            for (int i = tid; i < gn * NW * 64; i += NTH) { acc_c[i] = 0.0; acc_s[i] = 0.0; }
             lds_barrier();
-            lin_cand_batch(pose_mat + (size_t)cur * prm.P * 12, cpose, prm.P - 1, U, ncam, gn, (int)(wd - dsm),
+            lin_cand_batch<NTH>(pose_mat + (size_t)cur * prm.P * 12, cpose, prm.P - 1, U, ncam, gn, (int)(wd - dsm),
                            (int)(cand - dsm), (int)(tabs - dsm), per_tab, (int)(wext - dsm));
             lds_barrier();
-            for (int sbi = (int)sb_begin + wave; sbi < (int)sb_end; sbi += LH_WAVES) {
+            for (int sbi = (int)sb_begin + wave; sbi < (int)sb_end; sbi += NW) {
                 const lh_subbatch S = S_n;
                 const int lg = S.lg, nlm = S.n_lm;
                 const int ls = lane >> lg, gj = lane & ((1 << lg) - 1);
@@ -445,7 +454,7 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
                 const int wfl = wfl_n;
                 const int o = sbi * 64 + lane;
                 {   // the next sub-batch's words: after the wave's last one, its first again (the next group's)
-                    const int sbw = sbi + LH_WAVES < (int)sb_end ? sbi + LH_WAVES : (int)sb_begin + wave;
+                    const int sbw = sbi + NW < (int)sb_end ? sbi + NW : (int)sb_begin + wave;
                     const int sbn = min(sbw, sb_last);
                     const int on = sbn * 64 + lane;
                     S_n = sbs[sbn];
@@ -475,7 +484,7 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
                 if (live) backsub_jac<F32>(wt_c + (slot * ncam + cam) * LH_PT_LDS, e, ext_id, ext_rot, u, v, wfl, X, prm, E);
                 for (int r = 0; r < gn; ++r) {
                     double Xr[3] = {X[0], X[1], X[2]};
-                    const int ai = (r * LH_WAVES + wave) * 64 + lane;
+                    const int ai = (r * NW + wave) * 64 + lane;
                     double sa = acc_s[ai];
                     backsub_apply(E, live, wd + r * 6 * U + 6 * slot, lg, lmok, lead, cl, lam_l[g0 + r], prm, Xr, sa);
                     acc_s[ai] = sa;
@@ -491,19 +500,24 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
                 }
             }
             // each rung's wave totals (the single-trial path's butterflies), then its chunk scalars in that path's
-            // combine order, (w0 + w2) + (w1 + w3)
+            // combine order (below)
             for (int r = 0; r < gn; ++r) {
-                const int ai = (r * LH_WAVES + wave) * 64 + lane;
+                const int ai = (r * NW + wave) * 64 + lane;
                 double t3[3] = {acc_c[ai], acc_s[ai], 0.0};
                 group_sum(t3, 6);
-                if (lane == 0) { wtot[(r * LH_WAVES + wave) * 2] = t3[0]; wtot[(r * LH_WAVES + wave) * 2 + 1] = t3[1]; }
+                if (lane == 0) { wtot[(r * NW + wave) * 2] = t3[0]; wtot[(r * NW + wave) * 2 + 1] = t3[1]; }
             }
             lds_barrier();
-            for (int i = tid; i < gn * 4; i += 256) {
+            for (int i = tid; i < gn * 4; i += NTH) {
                 const int r = i >> 2, k = i & 3;
-                const double* wt = wtot + r * LH_WAVES * 2;
-                csc[((size_t)(g0 + r) * prm.n_chunks + chunk) * 4 + k] =
-                    k < 2 ? (wt[0 * 2 + k] + wt[2 * 2 + k]) + (wt[1 * 2 + k] + wt[3 * 2 + k]) : 0.0;
+                const double* wt = wtot + r * NW * 2;
+                double v = 0.0;
+                if (k < 2) {
+                    if constexpr (NW == 4) v = (wt[0 * 2 + k] + wt[2 * 2 + k]) + (wt[1 * 2 + k] + wt[3 * 2 + k]);
+                    else v = ((wt[0 * 2 + k] + wt[4 * 2 + k]) + (wt[2 * 2 + k] + wt[6 * 2 + k])) +
+                             ((wt[1 * 2 + k] + wt[5 * 2 + k]) + (wt[3 * 2 + k] + wt[7 * 2 + k]));
+                }
+                csc[((size_t)(g0 + r) * prm.n_chunks + chunk) * 4 + k] = v;
             }
         }
         return;
@@ -511,7 +525,7 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
     // A trial's candidate pose tables (wt_n): wave cwave composes the window's candidate poses (lane = slot)
     // and their tables (lane = (slot, camera)) while the other waves start their first back
     // substitution, which needs only the committed tables; they wait on cflag before their first
-    // evaluation at the candidate.  Waves 2 and 3 run one sub-batch fewer than wave 0 in most chunks.
+    // evaluation at the candidate.  The last waves run one sub-batch fewer than wave 0 in most chunks.
     if (TRIAL && !relin && wave == cwave) {
         if (lane < U) {
             double To[12];
@@ -530,9 +544,10 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         __hip_atomic_store(cflag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     bool tabs_ready = !TRIAL || relin;
+    LSTAMP_DECL(TRIAL && !evo && !relin, (int)blockIdx.x - (writer ? 1 : 0), NW, wave)
     const double* wt_l = relin ? wt_c : wt_n;   // the tables the edges are evaluated and linearised at
 
-    for (; sb < (int)sb_end; sb += LH_WAVES) {
+    for (; sb < (int)sb_end; sb += NW) {
         const lh_subbatch S = S_n;       // scalar words, prefetched one sub-batch ahead (sb is wave-uniform)
         const int lg = S.lg, nlm = S.n_lm;
         const int ls = lane >> lg, gj = lane & ((1 << lg) - 1);
@@ -544,7 +559,7 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         const int wfl = wfl_n;
         const int o = sb * 64 + lane;
         {
-            const int sbn = min(sb + LH_WAVES, sb_last);
+            const int sbn = min(sb + NW, sb_last);
             const int on = sbn * 64 + lane;
             S_n = sbs[sbn];
             meta_n = obs_meta[on];
@@ -754,9 +769,13 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
         }
         wave_sync();
         STAMP(6);
+        LSTAMP_ROUND();
     }
 
-    // ---- combine the 4 waves, (w0 + w2) + (w1 + w3), and write the chunk slab ----
+    // ---- combine the waves in a fixed order and write the chunk slab.  NS = NW / 2 slabs in LDS: wave w < NS
+    //      writes slab w, then wave w >= NS adds into slab w - NS, and the writers below add the slabs (s0..s3):
+    //      4 waves (w0 + w2) + (w1 + w3); 8 waves ((w0 + w4) + (w2 + w6)) + ((w1 + w5) + (w3 + w7)), every slab the
+    //      sum of one SIMD's two waves.  A wave without a sub-batch takes part with exact zeros. ----
     {   // the wave's totals: DPP and permlane butterflies (no LDS round trips); max |diag H_ll| likewise
         double t3[3] = {chi_acc, scale_acc, ndeg};
         group_sum(t3, 6);
@@ -766,24 +785,30 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
     STAMP(9);
     lds_barrier();
     STAMP(8);
+    constexpr int NS = NW / 2, LNS = NW == 8 ? 2 : 1;   // slabs, and log2 of them
     double* smem = dsm;
     if (evo) {   // the chunk's scalars only, combined in the same order as below
         for (int phase = 0; phase < 2; ++phase) {
-            if ((wave >> 1) == phase && lane == 0) {
-                double* sc = smem + (wave & 1) * 2;
+            if ((wave >> LNS) == phase && lane == 0) {
+                double* sc = smem + (wave & (NS - 1)) * 2;
                 if (phase == 0) { sc[0] = chi_acc; sc[1] = scale_acc; }
                 else { sc[0] += chi_acc; sc[1] += scale_acc; }
             }
             lds_barrier();
         }
         double* gs = csc + (size_t)chunk * 4;
-        if (tid < 2) gs[tid] = smem[tid] + smem[2 + tid];
+        if constexpr (NW == 4) {
+            if (tid < 2) gs[tid] = smem[tid] + smem[2 + tid];
+        } else {
+            if (tid < 2) gs[tid] = (smem[tid] + smem[4 + tid]) + (smem[2 + tid] + smem[6 + tid]);
+        }
         if (tid == 2 || tid == 3) gs[tid] = 0.0;
         return;
     }
+    static_assert(NW * Cfg::SCR >= NS * Cfg::LS, "the combine slabs fit the wave scratch");
     for (int phase = 0; phase < 2; ++phase) {
-        if ((wave >> 1) == phase) {
-            double* sl = smem + (wave & 1) * Cfg::LS;
+        if ((wave >> LNS) == phase) {
+            double* sl = smem + (wave & (NS - 1)) * Cfg::LS;
             const bool first = phase == 0;
 #pragma unroll
             for (int t = 0; t < Cfg::NT; ++t)
@@ -814,60 +839,81 @@ __global__ __launch_bounds__(256, (T <= 3) ? LH_LIN_OCC : 1) void k_lin(
     // landmark part of S block (p, q), row-major; diagonal pairs also [36, 69) the pose's 33 sums.
     const double* s0 = smem;
     const double* s1 = smem + Cfg::LS;
+    const double* s2 = smem + (NW == 8 ? 2 : 0) * Cfg::LS;   // (8 waves only)
+    const double* s3 = smem + (NW == 8 ? 3 : 0) * Cfg::LS;
     const uint32_t* wrow = reinterpret_cast<const uint32_t*>(wext + ncam * LH_EXT);
     {
         const int a = lane / 6, bb = lane - 6 * (lane / 6);
         int lp = 0;
         for (int s = 0; s < U; ++s)
             for (int t = s; t < U; ++t, ++lp) {
-                if ((lp & (LH_WAVES - 1)) != wave) continue;
+                if ((lp & (NW - 1)) != wave) continue;
                 double* row = rows + (size_t)wrow[lp] * LH_ROW;
                 if (lane < 36) {
                     int ra = 6 * s + a, rc = 6 * t + bb;
                     if ((ra >> 4) > (rc >> 4)) { const int x = ra; ra = rc; rc = x; }
                     const int R = ra >> 4, Cc = rc >> 4;
                     const int idx = (R * T - (R * (R - 1)) / 2 + (Cc - R)) * 256 + (ra & 15) * 16 + (rc & 15);
-                    st_out(row + lane, s0[idx] + s1[idx]);
+                    if constexpr (NW == 4) st_out(row + lane, s0[idx] + s1[idx]);
+                    else st_out(row + lane, (s0[idx] + s2[idx]) + (s1[idx] + s3[idx]));
                 }
-                if (s == t && lane < LH_TASKS)
-                    st_out(row + 36 + lane, s0[Cfg::LS_TASK + s * LH_TASKS + lane] + s1[Cfg::LS_TASK + s * LH_TASKS + lane]);
+                if (s == t && lane < LH_TASKS) {
+                    const int c = Cfg::LS_TASK + s * LH_TASKS + lane;
+                    if constexpr (NW == 4) st_out(row + 36 + lane, s0[c] + s1[c]);
+                    else st_out(row + 36 + lane, (s0[c] + s2[c]) + (s1[c] + s3[c]));
+                }
             }
     }
     double* gs = csc + (size_t)chunk * 4;
-    if (tid < 3) gs[tid] = s0[Cfg::LS_SC + tid] + s1[Cfg::LS_SC + tid];
-    if (tid == 3) gs[3] = fmax(s0[Cfg::LS_SC + 3], s1[Cfg::LS_SC + 3]);
+    if constexpr (NW == 4) {
+        if (tid < 3) gs[tid] = s0[Cfg::LS_SC + tid] + s1[Cfg::LS_SC + tid];
+        if (tid == 3) gs[3] = fmax(s0[Cfg::LS_SC + 3], s1[Cfg::LS_SC + 3]);
+    } else {
+        if (tid < 3) gs[tid] = (s0[Cfg::LS_SC + tid] + s2[Cfg::LS_SC + tid]) + (s1[Cfg::LS_SC + tid] + s3[Cfg::LS_SC + tid]);
+        if (tid == 3) gs[3] = fmax(fmax(s0[Cfg::LS_SC + 3], s2[Cfg::LS_SC + 3]), fmax(s1[Cfg::LS_SC + 3], s3[Cfg::LS_SC + 3]));
+    }
     STAMP(10);
     STAMP_FLUSH(0, 11);
 }
 
-// dynamic LDS of k_lin<T>: 4 wave scratches + the chunk's pose tables, step and extrinsics
+// dynamic LDS of k_lin<T, ., ., nw>: nw wave scratches + the chunk's pose tables, step and extrinsics
 template <int T>
-static size_t lin_smem_bytes(int ncam) {
+static size_t lin_smem_bytes(int ncam, int nw) {
     using Cfg = LinCfg<T>;
-    return sizeof(double) * ((size_t)LH_WAVES * Cfg::SCR + 2 * (size_t)Cfg::UMAX * ncam * LH_PT_LDS + Cfg::UMAX * 6 +
+    return sizeof(double) * ((size_t)nw * Cfg::SCR + 2 * (size_t)Cfg::UMAX * ncam * LH_PT_LDS + Cfg::UMAX * 6 +
                              (size_t)ncam * LH_EXT + (Cfg::UMAX * (Cfg::UMAX + 1) / 2 + 1) / 2 + 1);
 }
 
-// The one list of k_lin's instantiations, T = 1..6 x TRIAL x F32: the kernel of (T, trial, f32) and its LDS size
-// (a null kernel for a T outside the list).  Every launcher below goes through it.
+// The one list of k_lin's instantiations, T = 1..6 x TRIAL x F32 at 4 waves and T = 1..3 x TRIAL x F32 at 8: the
+// kernel of (T, trial, f32, waves) and its LDS size (a null kernel outside the list).  Every launcher below goes
+// through it.
 struct LinInst {
-    decltype(&k_lin<1, false, false>) fn;
-    size_t (*smem)(int ncam);
+    decltype(&k_lin<1, false, false, 4>) fn;
+    size_t (*smem)(int ncam, int nw);
 };
-template <int T>
+template <int T, int NW>
 static LinInst lin_inst_t(bool trial, bool f32) {
-    return {trial ? (f32 ? k_lin<T, true, true> : k_lin<T, true, false>)
-                  : (f32 ? k_lin<T, false, true> : k_lin<T, false, false>),
+    return {trial ? (f32 ? k_lin<T, true, true, NW> : k_lin<T, true, false, NW>)
+                  : (f32 ? k_lin<T, false, true, NW> : k_lin<T, false, false, NW>),
             lin_smem_bytes<T>};
 }
-static LinInst lin_inst(int T, bool trial, bool f32) {
+static LinInst lin_inst(int T, bool trial, bool f32, int nw) {
+    if (nw == 8) {
+        switch (T) {
+            case 1: return lin_inst_t<1, 8>(trial, f32);
+            case 2: return lin_inst_t<2, 8>(trial, f32);
+            case 3: return lin_inst_t<3, 8>(trial, f32);
+            default: return {nullptr, nullptr};
+        }
+    }
+    if (nw != LH_WAVES) return {nullptr, nullptr};
     switch (T) {
-        case 1: return lin_inst_t<1>(trial, f32);
-        case 2: return lin_inst_t<2>(trial, f32);
-        case 3: return lin_inst_t<3>(trial, f32);
-        case 4: return lin_inst_t<4>(trial, f32);
-        case 5: return lin_inst_t<5>(trial, f32);
-        case 6: return lin_inst_t<6>(trial, f32);
+        case 1: return lin_inst_t<1, 4>(trial, f32);
+        case 2: return lin_inst_t<2, 4>(trial, f32);
+        case 3: return lin_inst_t<3, 4>(trial, f32);
+        case 4: return lin_inst_t<4, 4>(trial, f32);
+        case 5: return lin_inst_t<5, 4>(trial, f32);
+        case 6: return lin_inst_t<6, 4>(trial, f32);
         default: return {nullptr, nullptr};
     }
 }
@@ -877,26 +923,31 @@ static LinInst lin_inst(int T, bool trial, bool f32) {
 // ============================================================================
 extern "C" {
 
-// dynamic LDS of k_lin<T> for ncam cameras (the host rejects windows whose chunks would not fit a CU)
-size_t lh_lin_smem(int T, int ncam) {
-    const LinInst k = lin_inst(T, false, false);
-    return k.fn ? k.smem(ncam) : (size_t)-1;
+// dynamic LDS of k_lin<T> at nw waves for ncam cameras (the host rejects windows whose chunks would not fit a CU,
+// and the planner keeps 4 waves where 8 would not); (size_t)-1 for a shape that does not exist
+size_t lh_lin_smem(int T, int ncam, int nw) {
+    const LinInst k = lin_inst(T, false, false, nw);
+    return k.fn ? k.smem(ncam, nw) : (size_t)-1;
 }
 
 // Raise the dynamic-LDS limit of every k_lin instantiation on the current device (lh_create) to the
 // device's per-workgroup LDS (hipDeviceAttributeMaxSharedMemoryPerBlock, read once by the host, which
 // also rejects windows whose chunks would exceed it), before any launch.
 hipError_t lh_prepare_lin(int lds_limit) {
-    for (int T = 1; T <= 6; ++T)
-        for (int v = 0; v < 4; ++v) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lin_inst(T, v & 1, v >> 1).fn),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
-            if (e != hipSuccess) return e;
-        }
+    for (int nw = LH_WAVES; nw <= LH_WAVES_WG8; nw += LH_WAVES)
+        for (int T = 1; T <= 6; ++T)
+            for (int v = 0; v < 4; ++v) {
+                const LinInst k = lin_inst(T, v & 1, v >> 1, nw);
+                if (!k.fn) continue;
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+                if (e != hipSuccess) return e;
+            }
     return hipSuccess;
 }
 
-hipError_t lh_launch_lin(int T, int trial, int nchunks, int chunk_base, hipStream_t st, const lh_chunk* chunks,
+// nw: the waves per workgroup the window's plan chose (lh::Plan::lin_waves)
+hipError_t lh_launch_lin(int T, int nw, int trial, int nchunks, int chunk_base, hipStream_t st, const lh_chunk* chunks,
                          const lh_subbatch* sbs, const float* obs_uv, const uint32_t* obs_meta, double* rec,
                          double* ptab, const double* ext, const lh_ctrl* ctrl, const double* dxp,
                          double* edge_rho, double* rows, double* csc, const uint32_t* crow, uint8_t* wflag, long nslots,
@@ -904,14 +955,15 @@ hipError_t lh_launch_lin(int T, int trial, int nchunks, int chunk_base, hipStrea
                          lh_reset_args rst) {
     writer = writer ? 1 : 0;   // block 0 stores the trial's candidate poses and tables (the restart, initially)
     if (nchunks + writer <= 0) return hipSuccess;
-    dim3 g(nchunks + writer), b(256);
+    dim3 g(nchunks + writer), b(64 * nw);
     // (diagnostic) LH_TEST_LIN_LDS_PAD bytes of extra LDS per workgroup: fewer k_lin workgroups per CU, for the
     // latency-hiding probe of scripts/occupancy_probe.py
     static const size_t lds_pad = getenv("LH_TEST_LIN_LDS_PAD") ? (size_t)atol(getenv("LH_TEST_LIN_LDS_PAD")) : 0;
-    const LinInst k = lin_inst(T, trial != 0, prm.precision == 1);
+    const LinInst k = lin_inst(T, trial != 0, prm.precision == 1, nw);
     if (!k.fn) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k.fn, g, b, k.smem(prm.ncam) + lds_pad, st, chunks, sbs, obs_uv, obs_meta, rec, ptab, ext, ctrl, dxp,
-                       edge_rho, rows, csc, crow, wflag, nslots, prm, nrec, fixed_bits, chunk_base, pose_mat, writer, rst);
+    hipLaunchKernelGGL(k.fn, g, b, k.smem(prm.ncam, nw) + lds_pad, st, chunks, sbs, obs_uv, obs_meta, rec, ptab, ext, ctrl,
+                       dxp, edge_rho, rows, csc, crow, wflag, nslots, prm, nrec, fixed_bits, chunk_base, pose_mat, writer,
+                       rst);
     return hipGetLastError();
 }
 

@@ -189,6 +189,7 @@ inline int pair_index(const Plan& pl, int p, int q) {
 // plan_structure
 // ---------------------------------------------------------------------------------------------
 int plan_structure(const lh_window* w, const PlanCfg& cfg, bool allow_empty, Plan& pl, Pool* pool) {
+    pl.lin_waves = LH_WAVES;   // (a reused plan: an early return leaves no stale shape)
     if (!w) return LH_E_BADARG;
     if (w->n_poses < 0 || w->n_landmarks < 0 || w->n_obs < 0) return LH_E_BADARG;
     if (w->n_poses > 0 && !w->pose_Tcw) return LH_E_BADARG;
@@ -377,7 +378,9 @@ int plan_structure(const lh_window* w, const PlanCfg& cfg, bool allow_empty, Pla
     //      count near 512 (C3: 104 landmarks, 488 chunks of 13 sub-batches, so one wave in four runs
     //      a fourth sub-batch).  Rounding to 32 gives 128 (398 chunks: 142 CUs run two chunks of
     //      4 sub-batches per wave, 114 run one), and 96 gives 528 chunks (16 wait for a free slot).
-    //      Measured on C3: k_lin 41.2 us at 104, 44.0 at 128, 51.6 at 96. ----
+    //      Measured on C3: k_lin 41.2 us at 104, 44.0 at 128, 51.6 at 96.  This is the 4-wave plan; a window that
+    //      fills the GPU is cut again for the 8-wave shape below (C3: 247 chunks of 26 sub-batches, k_lin 38.3 ->
+    //      34.9 us in-solve). ----
     int chunk_lm = (Lact + 511) / 512;
     chunk_lm = ((chunk_lm + LH_SB_LM - 1) / LH_SB_LM) * LH_SB_LM;
     chunk_lm = std::max(32, std::min(256, chunk_lm));
@@ -469,18 +472,73 @@ int plan_structure(const lh_window* w, const PlanCfg& cfg, bool allow_empty, Pla
         seg.push_back(Lact);
     }
     const int nseg = (int)seg.size() - 1;
-    std::vector<Cut> cuts((size_t)std::max(nseg, 1));
-    if (pool && nseg > 1) pool->run(nseg, [&](int k) { cut_range(seg[k], seg[k + 1], cuts[k]); });
-    else for (int k = 0; k < nseg; ++k) cut_range(seg[k], seg[k + 1], cuts[k]);
-    bool joined = true;
-    for (int k = 1; k < nseg && joined; ++k) {
-        uint64_t m;
-        joined = fresh_at(cuts[k - 1], seg[k], m);
+    auto cut_all = [&]() {   // the chunks at the current chunk_lm
+        std::vector<Cut> cuts((size_t)std::max(nseg, 1));
+        if (pool && nseg > 1) pool->run(nseg, [&](int k) { cut_range(seg[k], seg[k + 1], cuts[k]); });
+        else for (int k = 0; k < nseg; ++k) cut_range(seg[k], seg[k + 1], cuts[k]);
+        bool joined = true;
+        for (int k = 1; k < nseg && joined; ++k) {
+            uint64_t m;
+            joined = fresh_at(cuts[k - 1], seg[k], m);
+        }
+        if (!joined) {   // a chunk would run across a cut: the serial pass
+            cuts.assign(1, Cut{});
+            cut_range(0, Lact, cuts[0]);
+        }
+        return cuts;
+    };
+    std::vector<Cut> cuts = cut_all();
+
+    // ---- k_lin's workgroup shape.  4 waves per workgroup, two workgroups per CU, is the plan above.  8 waves
+    //      (T <= 3, lh_lin.hip) put a CU's whole share into one workgroup, whose waves w and w + 4 share a SIMD:
+    //      sub-batch i of a chunk runs on wave i mod 8, so the waves that run one sub-batch more than the rest sit
+    //      on distinct SIMDs where two 4-wave workgroups placed them by the dispatcher's choice.
+    //      Chosen for an auto-chunked window that fills the GPU (more 4-wave chunks than CUs), every chunk T <= 3 in
+    //      both plans, the 8-wave LDS within the device's limit, and at most kWg8ChunkLm landmarks per chunk at one
+    //      chunk per CU (the 256 clamp is raised to it for this shape only; a larger window, C4 say, runs several
+    //      rounds of workgroups either way and keeps 4 waves).  The chunks are cut again at ceil(L / CUs) landmarks,
+    //      raised until the cuts where the first pose moves leave at most one chunk per CU (C3 on 256 CUs: 208
+    //      landmarks, 26 sub-batches).  Any other window keeps the plan above exactly. ----
+    constexpr int kWg8ChunkLm = 512;
+    auto count_chunks = [](const std::vector<Cut>& cs) {
+        size_t n = 0;
+        for (const Cut& c : cs) n += c.mask.size();
+        return (int)n;
+    };
+    auto wg8_fits = [&](const std::vector<Cut>& cs) {   // every chunk T <= 3 and within the LDS limit at 8 waves
+        int tmax = 0;
+        for (const Cut& c : cs)
+            for (uint64_t m : c.mask) tmax = std::max(tmax, chunk_tiles(m));
+        if (tmax < 1 || tmax > 3) return false;
+        return !cfg.lin_smem || cfg.lin_smem(tmax, pl.ncam, LH_WAVES_WG8) <= cfg.lds_limit;
+    };
+    pl.lin_waves = LH_WAVES;
+    const int n_cu = std::max(cfg.n_cu, 1);
+    if (cfg.force_wg8) {
+        if (wg8_fits(cuts)) pl.lin_waves = LH_WAVES_WG8;
+    } else if (!cfg.no_wg8 && cfg.chunk_lm == 0 && count_chunks(cuts) > n_cu && wg8_fits(cuts)) {
+        const int lm4 = chunk_lm;
+        int target = n_cu;
+        for (int attempt = 0; attempt < 4 && pl.lin_waves == LH_WAVES; ++attempt) {
+            int lm8 = (Lact + target - 1) / target;
+            lm8 = ((lm8 + LH_SB_LM - 1) / LH_SB_LM) * LH_SB_LM;
+            if (lm8 <= lm4 || lm8 > kWg8ChunkLm) break;
+            chunk_lm = lm8;
+            std::vector<Cut> c8 = cut_all();
+            const int n8 = count_chunks(c8);
+            if (n8 <= n_cu) {
+                if (wg8_fits(c8)) { cuts.swap(c8); pl.lin_waves = LH_WAVES_WG8; }
+                break;
+            }
+            // the cuts the size bound does not make (first-pose changes) took n8 - ceil(L / lm8) chunks: leave room
+            const int forced = n8 - (Lact + lm8 - 1) / lm8;
+            const int next = std::min(target - 1, n_cu - std::max(forced, 1));
+            if (next < 1) break;
+            target = next;
+        }
+        if (pl.lin_waves == LH_WAVES) chunk_lm = lm4;
     }
-    if (!joined) {   // a chunk would run across a cut: the serial pass
-        cuts.assign(1, Cut{});
-        cut_range(0, Lact, cuts[0]);
-    }
+    pl.chunk_lm = chunk_lm;
     std::vector<int32_t> c_sb0;              // per chunk (creation order): its first sub-batch
     std::vector<int32_t> t_first;            // sub-batches in creation order: first position
     std::vector<uint8_t> t_lg;
@@ -732,6 +790,9 @@ Switches read_switches() {
     s.ladder_lazy = getenv("LH_LADDER_LAZY") != nullptr;
     s.no_bimg = getenv("LH_NO_BIMG") != nullptr;
     s.no_img = getenv("LH_NO_IMG") != nullptr;
+    s.no_lin_wg8 = getenv("LH_NO_LIN_WG8") != nullptr;
+    const char* t8 = getenv("LH_TEST_LIN_WG8");
+    s.test_lin_wg8 = t8 && t8[0] == '1';
     return s;
 }
 
@@ -786,6 +847,7 @@ int ladder_rungs(int max_trials, const Switches& sw) {
 
 int solve_config(const SolveIn& in, SolveConfig& c) {
     c = SolveConfig{};
+    c.lin_waves = in.lin_waves;
     const Switches& sw = in.sw;
     const int P = in.P, n = 6 * P;
     const bool ldlt = in.linear_solver == LH_SOLVER_LDLT;

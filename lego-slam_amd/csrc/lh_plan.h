@@ -58,8 +58,16 @@ class Pool {
 };
 
 struct PlanCfg {
-    int chunk_lm = 0;      // landmarks per chunk; 0 = auto (~512 chunks, 2 workgroups per CU)
+    int chunk_lm = 0;      // landmarks per chunk; 0 = auto (~512 chunks, 2 workgroups per CU; or the 8-wave shape)
     bool rank_invariant_pairs = false;   // P > LH_PMAX_WIN: list every pair within the 64-pose span (sharded solves)
+    // ---- k_lin's workgroup shape (Plan::lin_waves; plan_structure's chunking stage has the rule) ----
+    int n_cu = 256;        // the device's compute units (256 where there is no device: the CPU tests)
+    bool no_wg8 = false;   // Switches::no_lin_wg8: always 4 waves
+    bool force_wg8 = false;   // Switches::test_lin_wg8: 8 waves on any chunking whose chunks are all T <= 3
+    // k_lin's dynamic LDS for (T, cameras, waves) and the device's limit: 8 waves are refused where they do not
+    // fit (null: no device, every shape fits)
+    size_t (*lin_smem)(int T, int ncam, int nw) = nullptr;
+    size_t lds_limit = 0;
 };
 
 struct Plan {
@@ -70,6 +78,8 @@ struct Plan {
     int n_rec = 0;                      // landmark records (8 per sub-batch)
     int64_t n_slots = 0;                // observation slots (64 per sub-batch)
     int tgroup_begin[LH_TMAX + 2] = {0};
+    int lin_waves = LH_WAVES;           // waves per k_lin workgroup: LH_WAVES, or LH_WAVES_WG8 (every chunk T <= 3)
+    int chunk_lm = 0;                   // the landmarks-per-chunk bound the chunks were cut with
     uint64_t fixed_mask = 0;            // bit p: pose p < 64 is fixed (fixed_bits[0])
     std::vector<uint64_t> fixed_bits;   // [(P + 63) / 64] bit p % 64 of word p / 64: pose p is fixed
     std::vector<uint16_t> pair_list;    // [2 npairs] (p, q), p <= q, of each reduced-system block
@@ -144,7 +154,15 @@ struct Switches {
     bool ladder_lazy = false;     // LH_LADDER_LAZY: only a factor after a rejection builds the ladder
     bool no_bimg = false;         // LH_NO_BIMG: k_ctrl_b's loaders read the packed blocks, not k_reduce's band image
     bool no_img = false;          // LH_NO_IMG: k_ctrl scatters the packed system, not k_reduce's LDS image
+    bool no_lin_wg8 = false;      // LH_NO_LIN_WG8: k_lin keeps 4 waves per workgroup on a window that fills the GPU
+    bool test_lin_wg8 = false;    // LH_TEST_LIN_WG8=1 (tests): k_lin's 8-wave shape on any window of T <= 3 chunks,
+                                  // whatever its chunking
 };
+// the switches that enter the plan itself
+inline void apply_switches(PlanCfg& cfg, const Switches& sw) {
+    cfg.no_wg8 = sw.no_lin_wg8;
+    cfg.force_wg8 = sw.test_lin_wg8 && !sw.no_lin_wg8;
+}
 Switches read_switches();
 
 // pf[p]: pose p's first coupled pose, the lowest pose of any chunk window holding p (a chunk writes a
@@ -178,6 +196,7 @@ struct SolveIn {
     int P = 0;
     size_t n_brow_ent = 0;        // Plan::brow_ent.size()
     const int* pf = nullptr;      // [P] plan_envelope, united over the ranks
+    int lin_waves = LH_WAVES;     // Plan::lin_waves
     int linear_solver = LH_SOLVER_LDLT, max_trials = 1, world_size = 1;
     bool rccl = false;            // the trials' exchange is an RCCL all-reduce
     Switches sw;
@@ -185,6 +204,7 @@ struct SolveIn {
 
 struct SolveConfig {
     int kind = LH_CTRL_LDS;       // lh_ctrl_kind: the controller kernel
+    int lin_waves = LH_WAVES;     // k_lin's waves per workgroup (the plan's choice; every k_lin launch follows it)
     bool band_narrow = false;     // k_ctrl_b: every row's envelope starts within 56 rows of its 8-row block
     bool band_lu = false;         // k_ctrl_b: some step needs the stream loaders as unit waves too
     int ladder = 1, batch = 1;    // lambda-ladder rungs; evaluate-only rungs per batch

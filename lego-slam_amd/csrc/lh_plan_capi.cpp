@@ -15,6 +15,24 @@ double now_ms() {
 
 extern "C" {
 
+// The plan entry points below plan as an upload does on a device of PlanCfg's default CU count: the environment
+// switches that enter the plan (LH_NO_LIN_WG8, LH_TEST_LIN_WG8) are read per call.
+
+// k_lin's workgroup shape on window `w` for a device of n_cu compute units (<= 0: PlanCfg's default):
+// out4 = {waves per workgroup, n_chunks, the landmarks-per-chunk bound, the CU count planned for}
+int lhp_plan_shape(const lh_window* w, int chunk_lm, int threads, int n_cu, int32_t* out4) {
+    lh::Pool pool(threads > 0 ? threads : 1);
+    lh::Plan pl;
+    lh::PlanCfg cfg;
+    cfg.chunk_lm = chunk_lm;
+    if (n_cu > 0) cfg.n_cu = n_cu;
+    lh::apply_switches(cfg, lh::read_switches());
+    const int st = lh::plan_structure(w, cfg, false, pl, &pool);
+    if (st != LH_OK) return st;
+    out4[0] = pl.lin_waves; out4[1] = pl.n_chunks; out4[2] = pl.chunk_lm; out4[3] = cfg.n_cu;
+    return LH_OK;
+}
+
 // sizes[0..6] = n_chunks, n_sb, n_items, npairs, n_rec, n_slots, fixed_mask; tgroup[0..LH_TMAX+1]
 // rank_invariant: the block list a landmark-sharded (world_size > 1) handle uses past LH_PMAX_WIN poses
 int lhp_plan_sizes(const lh_window* w, int chunk_lm, int threads, int64_t* sizes, int32_t* tgroup, int rank_invariant) {
@@ -23,6 +41,7 @@ int lhp_plan_sizes(const lh_window* w, int chunk_lm, int threads, int64_t* sizes
     lh::PlanCfg cfg;
     cfg.chunk_lm = chunk_lm;
     cfg.rank_invariant_pairs = rank_invariant != 0;
+    lh::apply_switches(cfg, lh::read_switches());
     const int st = lh::plan_structure(w, cfg, false, pl, &pool);
     if (st != LH_OK) return st;
     const int64_t v[7] = {pl.n_chunks, pl.n_sb, pl.n_items, pl.npairs, pl.n_rec, pl.n_slots, (int64_t)pl.fixed_mask};
@@ -39,6 +58,7 @@ int lhp_plan_fill(const lh_window* w, int chunk_lm, int threads, lh_chunk* chunk
     lh::PlanCfg cfg;
     cfg.chunk_lm = chunk_lm;
     cfg.rank_invariant_pairs = rank_invariant != 0;
+    lh::apply_switches(cfg, lh::read_switches());
     const int st = lh::plan_structure(w, cfg, false, pl, &pool);
     if (st != LH_OK) return st;
     lh::PlanOut po{chunks, sbs, meta, uv, obs_perm, lm_perm, items, pair_pq, rsmap, lm_xyz};
@@ -124,6 +144,7 @@ int lhp_solve_config(const lh_window* w, int linear_solver, int max_trials, int 
     lh::Plan pl;
     lh::PlanCfg cfg;
     cfg.rank_invariant_pairs = world_size > 1;
+    lh::apply_switches(cfg, lh::read_switches());
     int st = lh::plan_structure(w, cfg, world_size > 1, pl, nullptr);
     if (st != LH_OK) return st;
     const std::vector<int> env = lh::plan_envelope(pl);
@@ -131,6 +152,7 @@ int lhp_solve_config(const lh_window* w, int linear_solver, int max_trials, int 
     lh::SolveIn in;
     in.P = pl.P;
     in.n_brow_ent = pl.brow_ent.size();
+    in.lin_waves = pl.lin_waves;
     in.pf = env.data();
     in.linear_solver = linear_solver;
     in.max_trials = max_trials;
@@ -165,6 +187,7 @@ int lhp_reduce_table(const lh_window* w, int world_size, uint32_t* table, int32_
     lh::Plan pl;
     lh::PlanCfg cfg;
     cfg.rank_invariant_pairs = world_size > 1;
+    lh::apply_switches(cfg, lh::read_switches());
     const int st = lh::plan_structure(w, cfg, world_size > 1, pl, nullptr);
     if (st != LH_OK) return st;
     *n_blocks = lh::reduce_table(pl, lh::reduce_skip(world_size, lh::read_switches()), table);

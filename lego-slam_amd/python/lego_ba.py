@@ -303,7 +303,7 @@ ABI_SYMBOLS = [
     "lh_klt_track", "lh_klt_stereo_landmarks", "lh_track_frame", "lh_insert_keyframe", "lh_covariance",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
-    "lh_debug_batch", "lh_debug_reduced_system",
+    "lh_debug_batch", "lh_debug_reduced_system", "lh_debug_lin_shape", "lh_debug_lin_stamps",
 ]
 
 _balib = None
@@ -360,6 +360,8 @@ def ba_lib():
         if hasattr(lib, "lh_debug_reduced_system"):
             lib.lh_debug_reduced_system.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                                     C.POINTER(C.c_int32)]
+        if hasattr(lib, "lh_debug_lin_shape"):
+            lib.lh_debug_lin_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         _balib = lib
     return _balib
 
@@ -887,6 +889,13 @@ class Solver:
         _check(ba_lib().lh_debug_time_lin(self.h, reps, C.byref(ms)), "lh_debug_time_lin")
         return ms.value
 
+    def lin_shape(self):
+        """k_lin's shape on the uploaded window (lh_debug_lin_shape): (waves per workgroup, chunks, the
+        landmarks-per-chunk bound the chunks were cut with)."""
+        w, c, lm = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(ba_lib().lh_debug_lin_shape(self.h, C.byref(w), C.byref(c), C.byref(lm)), "lh_debug_lin_shape")
+        return w.value, c.value, lm.value
+
     def controller(self):
         """The controller the uploaded window runs (lh_debug_controller): 'k_ctrl', 'k_ctrl_g', 'k_ctrl_p'
         or 'k_ctrl_b'."""
@@ -961,6 +970,16 @@ def debug_stamps(reset=True):
     out = (C.c_ulonglong * 256)()
     _check(lib.lh_debug_stamps(out, 256, int(reset)), "lh_debug_stamps")
     return np.array(out[:], dtype=np.uint64)
+
+
+def debug_lin_stamps(n=16384):
+    """k_lin's per-wave records from the LH_STAMPS diagnostic build (lh_debug_lin_stamps; zeros otherwise), as
+    [n / 8][8] uint64."""
+    lib = ba_lib()
+    lib.lh_debug_lin_stamps.argtypes = [C.c_void_p, C.c_int]
+    out = np.zeros(n, np.uint64)
+    _check(lib.lh_debug_lin_stamps(_ptr(out), n), "lh_debug_lin_stamps")
+    return out.reshape(-1, 8)
 
 
 def comm_unique_id():
@@ -1038,6 +1057,16 @@ def plan_window(w, chunk_lm=0, threads=1, rank_invariant=False):
            "lhp_plan_fill")
     out.update(tgroup_begin=tg, fixed_mask=fixed_mask)
     return out
+
+
+def plan_shape(w, chunk_lm=0, threads=1, n_cu=0):
+    """k_lin's workgroup shape the planner chooses for window `w` on a device of n_cu compute units (0: the
+    planner's default, 256), the environment switches read as an upload reads them: dict(waves, n_chunks,
+    chunk_lm: the landmarks-per-chunk bound, n_cu)."""
+    ref = _WindowRef(w)
+    v = np.zeros(4, np.int32)
+    _check(_pl().lhp_plan_shape(C.byref(ref.s), int(chunk_lm), int(threads), int(n_cu), _ptr(v)), "lhp_plan_shape")
+    return dict(zip(("waves", "n_chunks", "chunk_lm", "n_cu"), (int(x) for x in v)))
 
 
 def ctrl_units(n, fcb, band=False):

@@ -12,7 +12,7 @@ import sys
 
 path, out, workload = sys.argv[1], sys.argv[2], sys.argv[3]
 reps = int(sys.argv[4]) if len(sys.argv) > 4 else 50
-rows = [r for r in csv.DictReader(open(path)) if r["Kernel_Name"].startswith("void k_lin<3, true, false>")]
+rows = [r for r in csv.DictReader(open(path)) if r["Kernel_Name"].startswith("void k_lin<3, true, false")]
 dur = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1000.0 for r in rows]
 replay = dur[-reps:]
 solve = [d for d in dur[:-(reps + 1)] if d > 25.0]
