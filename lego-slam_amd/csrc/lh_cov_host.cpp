@@ -20,6 +20,9 @@ bool pose_held(const lh_handle* h, int p, int anchor) {
 }
 
 int covariance_impl(lh_handle* h, const lh_cov_input* in, lh_cov_result* out) {
+    if (!h || !in || !out) return LH_E_BADARG;
+    FrontendCall call(h);
+    STAGE(call.select());
     if (!h->uploaded || !h->solved) return LH_E_STATE;
     if (h->opt.world_size > 1 || h->P > LH_PMAX_WIN) return LH_E_UNSUPPORTED;
     const int P = h->P, anchor = in->anchor, n6 = 6 * P;
@@ -50,10 +53,7 @@ int covariance_impl(lh_handle* h, const lh_cov_input* in, lh_cov_result* out) {
     double* d_blk = out->pose_cov ? cv.out.p + o_blk : cv.full.p + (size_t)n6 * n6;
     double* d_full = out->pose_cov_full ? cv.out.p + o_full : cv.full.p;
 
-    hipEvent_t e0 = next_event(h), e1 = next_event(h);
-    h->event_next = 0;
-    if (!e0 || !e1) return LH_E_HIP;
-    HIPCHK(hipEventRecord(e0, s));
+    STAGE(call.start());
     // ---- the linearisation at the returned state ----
     const lh_cov_snap_args sn{h->d_ctrl.p, h->d_qt.p, h->d_ptab.p, h->d_rec.p, h->d_lm_perm.p, P, npt, (int32_t)nrec,
                               cv.qt_init.p, cv.ptab_init.p, cv.lm.p};
@@ -87,12 +87,10 @@ int covariance_impl(lh_handle* h, const lh_cov_input* in, lh_cov_result* out) {
                                 h->d_lm_perm.p, cv.rowmap.p, d_full, cv.out.p, cv.out.p + o_lm, h->plan.n_sb, P};
         HIPCHK(lh_launch_cov_lm(s, &la, h->prm));
     }
-    HIPCHK(hipEventRecord(e1, s));
+    STAGE(call.stop());
     HIPCHK(hipMemcpyAsync(h->s_out.p, cv.out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out->time_ms = ms;
+    STAGE(call.time(&out->time_ms));
     const double* r = h->s_out.p;
     out->min_pivot = r[LH_COV_R_MINP];
     out->max_pivot = r[LH_COV_R_MAXP];
@@ -109,11 +107,5 @@ int covariance_impl(lh_handle* h, const lh_cov_input* in, lh_cov_result* out) {
 }  // namespace
 
 extern "C" int lh_covariance(lh_handle* h, const lh_cov_input* in, lh_cov_result* out) {
-    if (!h || !in || !out) return LH_E_BADARG;
-    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
-    try {
-        return covariance_impl(h, in, out);
-    } catch (...) {
-        return LH_E_HIP;
-    }
+    return no_throw(covariance_impl, h, in, out);
 }

@@ -1,7 +1,8 @@
 // lh_handle.h — the handle behind include/lego_ba.h and the buffer types it is made of: internal to the library's
-// host files (lh_host.cpp: the solver; lh_frontend.cpp: the frontend).  DevBuf and HostBuf free their memory in their
-// destructors, so `delete h` frees every buffer of the handle.  Neither may live at namespace or static scope: its
-// destructor would then call into the HIP runtime during process teardown, after the runtime is gone.
+// host files (lh_host.cpp: the solver; lh_frontend.cpp and lh_frame.cpp: the frontend; lh_cov_host.cpp: lh_covariance).
+// DevBuf and HostBuf free their memory in their destructors, so `delete h` frees every buffer of the handle.  Neither
+// may live at namespace or static scope: its destructor would then call into the HIP runtime during process teardown,
+// after the runtime is gone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -62,7 +63,28 @@ struct P2pState {
     int *h_xerr = nullptr, *d_xerr = nullptr;   // host-mapped failure word (a peer's tag did not arrive)
 };
 
-// What the frontend entry points keep between calls (lh_frontend.cpp)
+// The resident image of lh_track_frame and lh_insert_keyframe (lh_frame.cpp): two pyramid buffers, rows packed to
+// `cols` bytes and sized for every level (lh::pyramid_bytes), of which img[cur] holds the last successful call's image
+// with levels 0 .. levels - 1 built.  The protocol of a call that uses it: invalidate() before its first enqueue,
+// commit() once it has succeeded; a call that returns an argument or state error touches nothing.
+struct ResidentImage {
+    DevBuf<uint8_t> img[2];
+    bool matches(int c, int r) const { return valid && cols == c && rows == r; }
+    // the first level of img[cur]'s pyramid a call has to build: all above 0 of an image it is given, else those missing
+    int first_level_to_build(bool given) const { return given ? 1 : levels; }
+    int slot() const { return cur; }
+    void invalidate() { valid = false; }
+    void commit(int cur_, int cols_, int rows_, int levels_) {
+        cur = cur_; cols = cols_; rows = rows_; levels = levels_;
+        valid = true;
+    }
+
+private:
+    int cur = 0, cols = 0, rows = 0, levels = 0;
+    bool valid = false;
+};
+
+// What the frontend entry points keep between calls (lh_frontend.cpp, lh_frame.cpp)
 struct FrontendState {
     // frontend pose-only batch (lh_estimate_pose)
     // inputs and outputs each packed into one arena, so a call is one upload and one download
@@ -82,21 +104,17 @@ struct FrontendState {
     DevBuf<float> g_excl, g_kp;
     DevBuf<lh_gftt_ctl> g_ctl;
     HostBuf<lh_gftt_ctl> s_gctl;   // pinned: read back once per batch of selection rounds
-    // one frame of Frontend::Track (lh_track_frame).  The resident image: two pyramids, rows packed to r_cols bytes and
-    // sized for every level, of which r_img[r_cur] holds the last successful call's img2 with levels 0 .. r_levels - 1
-    // built (r_valid); a call reads it as img1 and makes its own img2 the other one.  lh_insert_keyframe reads it as its
-    // left image, or replaces it with the one it is given; no other entry point touches them.
-    DevBuf<uint8_t> r_img[2];
-    int r_cur = 0, r_cols = 0, r_rows = 0, r_levels = 0;
-    bool r_valid = false;
-    // its arenas: one upload (pose, points, keypoints, has_point), one download (pose, counts, kp2, success, the
-    // edge -> feature list, the edges' flags and chi2), and k_frames' inputs as k_track_pack writes them
+    // one frame of Frontend::Track (lh_track_frame).  The resident image is the last successful call's img2; a call
+    // reads it as img1 and makes its own img2 the other buffer.  lh_insert_keyframe reads it as its left image, or
+    // replaces it with the one it is given; no other entry point touches it.
+    ResidentImage res;
+    // its arenas (lh_frontend_layout.h TrackLayout): one upload, one download, and k_frames' inputs as k_track_pack
+    // writes them
     DevBuf<uint8_t> tk_in, tk_out, tk_work;
     HostBuf<uint8_t> s_tkin, s_tkout;
     // a keyframe's half of the frame (lh_insert_keyframe).  Its left image is the resident one above, which the detector
-    // and the tracker read in place; the right image's pyramid (the resident layout) is this call's own.  One upload
-    // arena (the cameras, the features' points and has_point bytes, have_kp with room for the corners behind it: the
-    // feature list), one download arena (counts, pt, kp_right, the corners, success, flags), the slots' states.
+    // and the tracker read in place; the right image's pyramid (the resident layout) is this call's own.  One input
+    // arena and one download arena (KeyframeLayout), the slots' states.
     DevBuf<uint8_t> kf_right, kf_in, kf_out, kf_state;
     HostBuf<uint8_t> s_kfin, s_kfout;
 };
@@ -245,6 +263,41 @@ inline bool g_debug = getenv("LH_DEBUG") != nullptr;
 
 // the next event of the handle's pool (nullptr: none could be created); the taker puts the pool back (event_next = 0)
 hipEvent_t next_event(lh_handle* h);
+
+// One call on the handle's stream (the frontend's entry points, lh_covariance): the device selection, the two events
+// around its kernels (start() in front of the first, stop() behind the last), time_ms once the stream has drained, and
+// on every way out (the error returns included) the handle's event pool put back.
+struct FrontendCall {
+    lh_handle* h;
+    hipStream_t s;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit FrontendCall(lh_handle* hh) : h(hh), s(hh->stream) {}
+    ~FrontendCall() { h->event_next = 0; }
+    int select() { return hipSetDevice(h->device) == hipSuccess ? LH_OK : LH_E_HIP; }
+    int record(hipEvent_t* e) {
+        if (!(*e = next_event(h))) return LH_E_HIP;
+        HIPCHK(hipEventRecord(*e, s));
+        return LH_OK;
+    }
+    int start() { return record(&e0); }
+    int stop() { return record(&e1); }
+    int time(double* time_ms) {   // after the call's last synchronise
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        *time_ms = ms;
+        return LH_OK;
+    }
+};
+
+// the staging copies build std::vectors (par_copy): no exception crosses the ABI
+template <typename In, typename Out>
+int no_throw(int (*impl)(lh_handle*, const In*, Out*), lh_handle* h, const In* in, Out* out) {
+    try {
+        return impl(h, in, out);
+    } catch (...) {
+        return LH_E_HIP;
+    }
+}
 
 // host copies between caller memory and pinned staging, in ~256 KB blocks over the planner's pool
 struct ByteSeg { void* dst; const void* src; size_t n; };

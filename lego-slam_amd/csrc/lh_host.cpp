@@ -1,6 +1,7 @@
 // lh_host.cpp — C ABI (include/lego_ba.h) of the MI355X BA solver: the handle's life (lh_handle.h), the upload of
 // a window (lh_plan.cpp preprocessing into pinned staging, one async copy per array), the LM launch loop, the per-trial
-// exchange of a landmark-sharded solve, the download of the results.  (The frontend entry points: lh_frontend.cpp.)
+// exchange of a landmark-sharded solve, the download of the results.  (The frontend entry points: lh_frontend.cpp and
+// lh_frame.cpp; lh_covariance: lh_cov_host.cpp.)
 //
 // Per solve nothing but kernel launches happens on the host: the whole LM loop (accept/reject,
 // lambda schedule, stop rule) runs on the device, and the host keeps `depth` trials enqueued ahead
@@ -15,6 +16,7 @@
 #include <cstring>
 #include <new>
 
+#include "lh_frontend_layout.h"
 #include "lh_handle.h"
 #include "lh_launch.h"
 
@@ -344,23 +346,28 @@ int bind_arena(lh_handle* h, bool band_possible) {
     h->n_slots = pl.n_slots;
     h->LY = lh_rs_make(P, pl.npairs);
     const size_t PT = (size_t)P * ncam * LH_PT;
-    size_t bytes = 0;
-    auto part = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
-    const size_t o_chunks = part(pl.n_chunks * sizeof(lh_chunk)), o_sbs = part((size_t)pl.n_sb * sizeof(lh_subbatch));
-    const size_t o_lmp = part((size_t)pl.n_rec * sizeof(int32_t)), o_pptr = part(((size_t)pl.npairs + 1) * sizeof(uint32_t));
-    const size_t o_items = part((size_t)pl.n_items * sizeof(uint32_t)), o_ppq = part(2 * (size_t)pl.npairs * sizeof(uint16_t));
-    const size_t o_rsmap = part((size_t)pl.npairs * 36 * sizeof(uint32_t)), o_ptab = part(2 * PT * sizeof(double));
-    const size_t o_qt = part(24 * (size_t)std::max(P, 1) * sizeof(double)), o_ext = part(LH_EXT * (size_t)ncam * sizeof(double));
-    const size_t o_fix = part(pl.fixed_bits.size() * sizeof(uint64_t)), o_bptr = part(pl.brow_ptr.size() * sizeof(int32_t));
-    const size_t o_bent = part(pl.brow_ent.size() * sizeof(uint32_t));
-    const size_t o_units = part(16 * LH_NSTEP * sizeof(uint16_t));
+    Arena ar;   // 256-byte aligned segments
+    const size_t o_chunks = ar.take(pl.n_chunks * sizeof(lh_chunk), 256);
+    const size_t o_sbs = ar.take((size_t)pl.n_sb * sizeof(lh_subbatch), 256);
+    const size_t o_lmp = ar.take((size_t)pl.n_rec * sizeof(int32_t), 256);
+    const size_t o_pptr = ar.take(((size_t)pl.npairs + 1) * sizeof(uint32_t), 256);
+    const size_t o_items = ar.take((size_t)pl.n_items * sizeof(uint32_t), 256);
+    const size_t o_ppq = ar.take(2 * (size_t)pl.npairs * sizeof(uint16_t), 256);
+    const size_t o_rsmap = ar.take((size_t)pl.npairs * 36 * sizeof(uint32_t), 256);
+    const size_t o_ptab = ar.take(2 * PT * sizeof(double), 256);
+    const size_t o_qt = ar.take(24 * (size_t)std::max(P, 1) * sizeof(double), 256);
+    const size_t o_ext = ar.take(LH_EXT * (size_t)ncam * sizeof(double), 256);
+    const size_t o_fix = ar.take(pl.fixed_bits.size() * sizeof(uint64_t), 256);
+    const size_t o_bptr = ar.take(pl.brow_ptr.size() * sizeof(int32_t), 256);
+    const size_t o_bent = ar.take(pl.brow_ent.size() * sizeof(uint32_t), 256);
+    const size_t o_units = ar.take(16 * LH_NSTEP * sizeof(uint16_t), 256);
     const size_t n_bunits = band_possible ? 16 * (size_t)lh::kBandSteps : 0, n_bblk = band_possible ? (size_t)P * 64 : 0;
-    const size_t o_bunits = part(n_bunits * sizeof(uint16_t));
-    const size_t o_bblk = part(n_bblk * sizeof(int32_t));
-    const size_t o_red = part(4 * ((size_t)pl.npairs + 1) * sizeof(uint32_t));
-    HIPCHK(h->d_arena.ensure(bytes));
-    HIPCHK(h->s_arena.ensure(bytes));
-    h->arena_bytes = bytes;
+    const size_t o_bunits = ar.take(n_bunits * sizeof(uint16_t), 256);
+    const size_t o_bblk = ar.take(n_bblk * sizeof(int32_t), 256);
+    const size_t o_red = ar.take(4 * ((size_t)pl.npairs + 1) * sizeof(uint32_t), 256);
+    HIPCHK(h->d_arena.ensure(ar.end));
+    HIPCHK(h->s_arena.ensure(ar.end));
+    h->arena_bytes = ar.end;
     auto bind = [](auto& d, auto& st, uint8_t* dbase, uint8_t* sbase, size_t off, size_t count) {
         using T = std::remove_pointer_t<decltype(d.p)>;
         d.p = reinterpret_cast<T*>(dbase + off); d.n = count;

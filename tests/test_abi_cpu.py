@@ -41,53 +41,50 @@ def test_no_hipify_or_dual_paths_in_sources():
         assert "__HIP_PLATFORM_AMD__" not in txt and "cuda" not in txt.lower(), f
 
 
-LAYOUT_C = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "lego_ba.h"
-#define P(s, f) printf(#s "." #f " %zu\n", offsetof(s, f));
-int main(void) {
-  printf("lh_options %zu\n", sizeof(lh_options));
-  printf("lh_window %zu\n", sizeof(lh_window));
-  printf("lh_result %zu\n", sizeof(lh_result));
-  printf("lh_kernel_stats %zu\n", sizeof(lh_kernel_stats));
-  printf("lh_frames %zu\n", sizeof(lh_frames));
-  printf("lh_frames_result %zu\n", sizeof(lh_frames_result));
-  P(lh_frames, obs_ptr) P(lh_frames, is_outlier) P(lh_frames, K)
-  P(lh_frames_result, iterations) P(lh_frames_result, time_ms)
-  P(lh_options, huber_delta) P(lh_options, linear_solver) P(lh_options, comm_id) P(lh_options, profile)
-  P(lh_options, pcg_max_iters) P(lh_options, pcg_tol)
-  P(lh_options, gate_mode) P(lh_options, chunk_landmarks) P(lh_options, comm_mode) P(lh_options, host_threads)
-  P(lh_options, allreduce) P(lh_options, allreduce_user) P(lh_options, precision)
-  P(lh_window, n_obs) P(lh_window, K) P(lh_window, cam_ext)
-  P(lh_result, trace_cap) P(lh_result, chi2_initial) P(lh_result, time_ms) P(lh_result, pcg_iterations)
-  P(lh_result, degenerate) P(lh_result, time_prep_ms) P(lh_result, time_upload_ms) P(lh_result, time_download_ms)
-  P(lh_result, is_outlier) P(lh_result, outlier_chi2_th) P(lh_result, outlier_th) P(lh_result, n_inlier)
-  P(lh_result, n_outlier)
-  return 0;
+# the fields the hand-written layout program checked before it was generated: the generated one covers at least these
+EARLIER_FIELDS = {
+    "lh_frames": "obs_ptr is_outlier K", "lh_frames_result": "iterations time_ms",
+    "lh_options": "huber_delta linear_solver comm_id profile pcg_max_iters pcg_tol gate_mode chunk_landmarks comm_mode "
+                  "host_threads allreduce allreduce_user precision",
+    "lh_window": "n_obs K cam_ext",
+    "lh_result": "trace_cap chi2_initial time_ms pcg_iterations degenerate time_prep_ms time_upload_ms time_download_ms "
+                 "is_outlier outlier_chi2_th outlier_th n_inlier n_outlier",
 }
-"""
+
+
+def mirrored_structs():
+    """{C name: class} of every ctypes.Structure lego_ba mirrors from include/lego_ba.h: LhFooBar is lh_foo_bar.
+    (LhwParams mirrors the window generator's header, not this one.)"""
+    return {re.sub(r"(?<!^)([A-Z])", r"_\1", name).lower(): c for name, c in vars(lego_ba).items()
+            if isinstance(c, type) and issubclass(c, C.Structure) and c is not C.Structure and name != "LhwParams"}
 
 
 def test_ctypes_struct_layout_matches_header(tmp_path):
-    c = tmp_path / "layout.c"
-    c.write_text(LAYOUT_C)
+    """sizeof of every mirrored struct and offsetof of every field, as a C compiler sees the header.  On a mismatch the
+    header is right."""
+    structs = mirrored_structs()
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "lego_ba.h"', "int main(void) {"]
+    for s, c in structs.items():
+        lines.append(f'  printf("{s} %zu\\n", sizeof({s}));')
+        lines += [f'  printf("{s}.{f} %zu\\n", offsetof({s}, {f}));' for f, *_ in c._fields_]
+    lines += ["  return 0;", "}"]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines) + "\n")
     exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    got = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    got = {k: int(v) for k, v in got.items()}
-    assert got["lh_options"] == C.sizeof(lego_ba.LhOptions)
-    assert got["lh_window"] == C.sizeof(lego_ba.LhWindow)
-    assert got["lh_result"] == C.sizeof(lego_ba.LhResult)
-    assert got["lh_kernel_stats"] == C.sizeof(lego_ba.LhKernelStats)
-    assert got["lh_frames"] == C.sizeof(lego_ba.LhFrames)
-    assert got["lh_frames_result"] == C.sizeof(lego_ba.LhFramesResult)
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = {k: int(v) for k, v in (line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())}
+    fields = {key for key in got if "." in key}
+    assert len(got) - len(fields) == len(structs) >= 22
+    assert len(fields) == sum(len(c._fields_) for c in structs.values())
+    assert {f"{s}.{f}" for s, names in EARLIER_FIELDS.items() for f in names.split()} <= fields
+    assert len(fields) >= 36
+    assert {"lh_options", "lh_window", "lh_result", "lh_kernel_stats", "lh_frames", "lh_frames_result"} <= set(structs)
     for key, v in got.items():
         if "." in key:
             s, f = key.split(".")
-            cls = {"lh_options": lego_ba.LhOptions, "lh_window": lego_ba.LhWindow, "lh_result": lego_ba.LhResult,
-                   "lh_frames": lego_ba.LhFrames, "lh_frames_result": lego_ba.LhFramesResult}[s]
-            assert getattr(cls, f).offset == v, key
+            assert getattr(structs[s], f).offset == v, key
+        else:
+            assert C.sizeof(structs[key]) == v, key
 
 
 def test_default_options_are_keyed_on_the_callers_abi():
