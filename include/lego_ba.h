@@ -688,6 +688,62 @@ typedef struct lh_cov_result {
 } lh_cov_result;
 int lh_covariance(lh_handle *h, const lh_cov_input *in, lh_cov_result *out);
 
+/* ---- a keyframe of a solved window marginalised into a prior on the poses that stay ----
+ *
+ * lh_marginalize works on the state the last lh_solve / lh_solve_resident on the handle returned, with the handle's
+ * weights and gate (Huber(huber_delta), gate_mode, precision) and identity information in pixels, as lh_covariance
+ * does.  With m = marg_pose:
+ *
+ *   M            the landmarks with a valid edge to pose m, whether or not m is fixed;
+ *   the system   of the edges of M's landmarks alone, to every pose they reach:
+ *                A_M = H_pp - H_pl H_ll^-1 H_lp, b_M = b_p - H_pl H_ll^-1 b_l, exactly what the solver's linearisation
+ *                forms for a window holding just those edges: no lambda, a fixed pose's rows and columns zero, the
+ *                solver's sign of b (the step solves A dx = b);
+ *   the earlier prior   prior_H / prior_b, when given, are added to A_M and b_M with the rows and columns of the
+ *                fixed poses zeroed first.  They are used as given: the caller has expressed them at this state.
+ *                Only prior_H's lower triangle (row >= col) is read;
+ *   the elimination   with r the rows of the other poses, H_prior = A[r, r] - A[r, m] A[m, m]^-1 A[m, r] and
+ *                b_prior = b[r] - A[r, m] A[m, m]^-1 b[m], by an unpivoted Cholesky A[m, m] = C C^T,
+ *                Y = C^-1 A[m, r], y = C^-1 b[m], H = A[r, r] - Y^T Y, g = b[r] - Y^T y.  No eigenvalue is thresholded:
+ *                a pivot that is not > 0 gives LH_E_SINGULAR with bad_row, and no output array is written;
+ *   a fixed m    nothing is eliminated: conditioning on it gives H_prior = A[r, r], b_prior = b[r]
+ *                (min_pivot = max_pivot = 0);
+ *   the layout   H_prior [6P][6P] and b_prior [6P] cover all P window poses in window order, so that the caller only
+ *                drops m's six rows and columns when the window slides, and the prior adds to the next window's system
+ *                as Hessian.topLeftCorner += H_prior, b.head += b_prior.  The rows and columns of m and of every fixed
+ *                pose are exact +0.0, and so are, without an earlier prior, those of every pose that shares no
+ *                landmark with m (an earlier prior's entries there pass through unchanged);
+ *   rank-deficient landmarks of M (fewer than two valid edges, or an H_ll that is not positive definite) are treated
+ *                as the solver treats them under degenerate_guard = 1: held fixed.  Their Schur terms
+ *                H_pl H_ll^-1 H_lp and H_pl H_ll^-1 b_l are dropped; their edges' H_pp and b_p stay.  They are counted
+ *                in n_degenerate.  On a handle with degenerate_guard = 0 and n_degenerate > 0 the call answers
+ *                LH_E_SINGULAR (bad_row 0), as lh_covariance does.
+ *
+ * H_prior equals its transpose by bits, two calls return the same bits, and the call changes nothing that a later
+ * solve, lh_covariance or lh_debug_reduced_system returns (it reads the solver's state and writes buffers of its own).
+ * A solve does not consume a prior yet: adding H_prior and b_prior to the system inside the LM loop is not part of
+ * this interface.
+ *
+ * LH_E_STATE: no completed solve of the uploaded window on the handle.  LH_E_BADARG: a null h, in, out, H_prior or
+ * b_prior, marg_pose outside [0, n_poses), one of prior_H / prior_b without the other.  LH_E_UNSUPPORTED: n_poses > 64,
+ * world_size > 1 (lh_covariance's envelope).  LH_E_SINGULAR: above; the counts and pivots are still reported. */
+typedef struct lh_marg_input {
+    int32_t marg_pose;            /* the pose to marginalise, 0 <= m < n_poses */
+    const double *prior_H;        /* [6P][6P] row-major or NULL: an earlier prior, added before the elimination; only the lower triangle (row >= col) is read */
+    const double *prior_b;        /* [6P] or NULL (both given or both NULL) */
+} lh_marg_input;
+typedef struct lh_marg_result {
+    double *H_prior;              /* [6P][6P] row-major (required) */
+    double *b_prior;              /* [6P] (required) */
+    uint8_t *lm_marginalised;     /* [n_landmarks] window order, or NULL: 1 = eliminated with the pose (the caller drops it from the map) */
+    int32_t n_landmarks, n_edges; /* landmarks eliminated; valid edges of those landmarks (all of them, to any pose) */
+    int32_t n_degenerate;         /* rank-deficient landmarks among them */
+    int32_t bad_row;              /* first row (0..5) of the eliminated block whose pivot was not > 0, else -1 */
+    double min_pivot, max_pivot;  /* L_ii^2 of the 6x6 factor */
+    double time_ms;               /* HIP-event bracket, linearisation included, download excluded */
+} lh_marg_result;
+int lh_marginalize(lh_handle *h, const lh_marg_input *in, lh_marg_result *out);
+
 /* ---- test hooks (not part of the reference interface) ---- */
 /* f64 MFMA accumulator-layout probe: D(16x16) = A(16x4) * B(4x16), device pointers, row-major */
 int lh_debug_mfma_probe(const double *A, const double *B, double *D);

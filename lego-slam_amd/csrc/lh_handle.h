@@ -1,5 +1,5 @@
 // lh_handle.h — the handle behind include/lego_ba.h and the buffer types it is made of: internal to the library's
-// host files (lh_host.cpp: the solver; lh_frontend.cpp and lh_frame.cpp: the frontend; lh_cov_host.cpp: lh_covariance).
+// host files (lh_host.cpp: the solver; lh_frontend.cpp and lh_frame.cpp: the frontend; lh_cov_host.cpp: lh_covariance; lh_marg_host.cpp: lh_marginalize).
 // DevBuf and HostBuf free their memory in their destructors, so `delete h` frees every buffer of the handle.  Neither
 // may live at namespace or static scope: its destructor would then call into the HIP runtime during process teardown,
 // after the runtime is gone.
@@ -119,16 +119,36 @@ struct FrontendState {
     HostBuf<uint8_t> s_kfin, s_kfout;
 };
 
-// What lh_covariance keeps between calls (lh_cov_host.cpp): a second set of lh_reset_args holding the last solve's
-// returned state, and everything its linearisation there writes that the solve's own state also holds (controller,
-// step, poses, tables, records, reduced system), so that the handle's solver state is only read
-struct CovState {
+// The returned state of the last solve, linearised again (lh_cov_host.cpp relin_enqueue; lh_covariance and
+// lh_marginalize each keep one): a second set of lh_reset_args holding that state, and everything the linearisation
+// there writes that the solve's own state also holds (controller, step, poses, tables, records, reduced system), so
+// that the handle's solver state is only read
+struct ReLin {
     DevBuf<double> qt_init, ptab_init, lm;     // the snapshot: lh_reset_args' three arrays
     DevBuf<double> qt, ptab, rec, dxp, rs, maxd;
     DevBuf<lh_ctrl> ctrl;
+};
+
+// What lh_covariance keeps between calls (lh_cov_host.cpp)
+struct CovState {
+    ReLin lin;
     DevBuf<int32_t> rowmap;
     DevBuf<double> A, W, full;                 // S[f, f] and its factor, L^-1, Sigma_pp (when it is not downloaded)
     DevBuf<double> out;                        // the download: the result block, then the arrays asked for
+};
+
+// What lh_marginalize keeps between calls (lh_marg_host.cpp): the observation words with the edges outside M masked
+// out, and the per-edge outputs of the linearisation on them (the solve's own rho0 and inlier flags stay as they are)
+struct MargState {
+    ReLin lin;
+    DevBuf<uint32_t> meta;
+    DevBuf<int32_t> counts;
+    DevBuf<double> rho;
+    DevBuf<uint8_t> wflag;
+    DevBuf<double> prior;                      // the earlier prior as uploaded: H [6P][6P], then b [6P]
+    HostBuf<double> s_prior;                   // its pinned staging
+    DevBuf<double> A, b, Y;                    // A_M + the earlier prior (lower), its right-hand side, C^-1 A[m, :] and C^-1 b[m]
+    DevBuf<double> out;                        // the download: the result block, H_prior, b_prior, lm_marginalised
 };
 
 }  // namespace lh
@@ -208,7 +228,8 @@ struct lh_handle {
     DevBuf<double> d_img;        // [2][LH_IMG_SZ] k_ctrl's LDS system image, staged / committed (prm.img)
     lh::FrontendState fe;
     lh::CovState cov;
-    bool solved = false;         // a solve of the uploaded window has completed (lh_covariance reads its state)
+    lh::MargState marg;
+    bool solved = false;         // a solve of the uploaded window has completed (lh_covariance, lh_marginalize read its state)
     lh_ctrl* h_ctrl = nullptr;   // pinned
     int last_chains = -1;        // lh_debug_chains: the last synchronous solve's stop chain
     int last_lskips = -1;        // lh_debug_ladder: its rejections onto a built ladder rung
@@ -302,5 +323,13 @@ int no_throw(int (*impl)(lh_handle*, const In*, Out*), lh_handle* h, const In* i
 // host copies between caller memory and pinned staging, in ~256 KB blocks over the planner's pool
 struct ByteSeg { void* dst; const void* src; size_t n; };
 void par_copy(lh_handle* h, const ByteSeg* seg, int nseg);
+
+// The linearisation at the state the last solve returned (lh_cov_host.cpp): relin_ensure sizes rl's buffers for the
+// uploaded window; relin_enqueue puts k_cov_snapshot, k_lin<T, false> and k_reduce (mode 0) on the handle's stream,
+// unchanged, writing rl alone: the lambda-free packed system in rl.rs, the records with chol(H_ll) in the second half
+// of rl.rec, the committed pose tables in rl.ptab_init.  meta: the observation words to linearise; rho [n_slots] and
+// wflag [2][n_slots]: where k_lin writes its per-edge rho0 and inlier flags; prm: k_lin's and k_reduce's parameters.
+int relin_ensure(lh_handle* h, ReLin& rl);
+int relin_enqueue(lh_handle* h, ReLin& rl, const uint32_t* meta, double* rho, uint8_t* wflag, const lh_params& prm);
 
 }  // namespace lh

@@ -1,7 +1,7 @@
 // lh_launch.h — the one declaration of every kernel launcher.  The definitions (lh_lin.hip, lh_kernels.hip and its lh_probe.hip, lh_frames.hip,
-// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip, lh_track.hip, lh_keyframe.hip, lh_cov.hip) and the callers (lh_host.cpp, lh_frontend.cpp, lh_cov_host.cpp) all include it: the symbols are extern "C", so only
+// lh_aux.hip, lh_lk.hip, lh_klt.hip, lh_tri.hip, lh_gftt.hip, lh_track.hip, lh_keyframe.hip, lh_cov.hip, lh_marg.hip) and the callers (lh_host.cpp, lh_frontend.cpp, lh_cov_host.cpp, lh_marg_host.cpp) all include it: the symbols are extern "C", so only
 // the compiler, seeing a definition beside this declaration, can tell that the two sides disagree.
-// (lh_tri.h, lh_gftt.h, lh_klt.h, lh_track.h and lh_cov.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.
+// (lh_tri.h, lh_gftt.h, lh_klt.h, lh_track.h, lh_cov.h and lh_marg.h are also compiled by plain g++ for the CPU probes and hold no HIP type: hence this header.
 // lh_keyframe.h holds its kernels' arguments alone, and no HIP type either.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 #include "lh_keyframe.h"
 #include "lh_klt.h"
 #include "lh_lk.h"
+#include "lh_marg.h"
 #include "lh_track.h"
 #include "lh_tri.h"
 
@@ -75,4 +76,6 @@ hipError_t lh_launch_kf_finish(hipStream_t st, const lh_kf_args* a);
 hipError_t lh_launch_cov_snapshot(hipStream_t st, const lh_cov_snap_args* a);
 hipError_t lh_launch_cov_pose(hipStream_t st, const lh_cov_args* a);
 hipError_t lh_launch_cov_lm(hipStream_t st, const lh_cov_lm_args* a, lh_params prm);
+hipError_t lh_launch_marg_mask(hipStream_t st, const lh_marg_mask_args* a);
+hipError_t lh_launch_marg_prior(hipStream_t st, const lh_marg_args* a);
 }

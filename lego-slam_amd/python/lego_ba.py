@@ -271,6 +271,16 @@ class LhCovResult(C.Structure):
                 ("bad_row", C.c_int32), ("min_pivot", C.c_double), ("max_pivot", C.c_double), ("time_ms", C.c_double)]
 
 
+class LhMargInput(C.Structure):
+    _fields_ = [("marg_pose", C.c_int32), ("prior_H", C.c_void_p), ("prior_b", C.c_void_p)]
+
+
+class LhMargResult(C.Structure):
+    _fields_ = [("H_prior", C.c_void_p), ("b_prior", C.c_void_p), ("lm_marginalised", C.c_void_p),
+                ("n_landmarks", C.c_int32), ("n_edges", C.c_int32), ("n_degenerate", C.c_int32), ("bad_row", C.c_int32),
+                ("min_pivot", C.c_double), ("max_pivot", C.c_double), ("time_ms", C.c_double)]
+
+
 class LhDetectInput(C.Structure):
     _fields_ = [
         ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int64), ("img", C.c_void_p), ("mask", C.c_void_p),
@@ -301,6 +311,7 @@ ABI_SYMBOLS = [
     "lh_kernel_stats_get", "lh_kernel_stats_reset", "lh_classify_outliers", "lh_set_profiling",
     "lh_estimate_pose", "lh_lk_track", "lh_triangulate", "lh_stereo_landmarks", "lh_detect_features",
     "lh_klt_track", "lh_klt_stereo_landmarks", "lh_track_frame", "lh_insert_keyframe", "lh_covariance",
+    "lh_marginalize",
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
     "lh_debug_batch", "lh_debug_reduced_system", "lh_debug_lin_shape", "lh_debug_lin_stamps",
@@ -347,6 +358,8 @@ def ba_lib():
             lib.lh_insert_keyframe.argtypes = [C.c_void_p, C.POINTER(LhKeyframeInput), C.POINTER(LhKeyframeResult)]
         if hasattr(lib, "lh_covariance"):
             lib.lh_covariance.argtypes = [C.c_void_p, C.POINTER(LhCovInput), C.POINTER(LhCovResult)]
+        if hasattr(lib, "lh_marginalize"):
+            lib.lh_marginalize.argtypes = [C.c_void_p, C.POINTER(LhMargInput), C.POINTER(LhMargResult)]
         lib.lh_classify_outliers.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lh_debug_event_floor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -518,6 +531,36 @@ class Solver:
             e = LhError(st, "lh_covariance")
             e.result = a
             raise e
+        return a
+
+    def marginalize(self, marg_pose, prior=None, out=None):
+        """lh_marginalize of the window last solved on this handle: pose `marg_pose` and the landmarks it observes
+        eliminated into a prior on the other poses.  prior: an earlier prior (H [6P, 6P], b [6P]) added before the
+        elimination, or None.  Returns H_prior [6P, 6P], b_prior [6P], lm_marginalised [L] (bool), n_landmarks, n_edges,
+        n_degenerate, bad_row, min_pivot, max_pivot, time_ms.  A singular eliminated block raises
+        LhError(LH_E_SINGULAR) with the result so far in its `result` attribute (no array is written).
+        out: a dict of preallocated arrays to write (H_prior, b_prior, lm_marginalised as uint8) instead of fresh ones."""
+        P, L = self._dims
+        out = {} if out is None else out
+        a = dict(H_prior=out.get("H_prior", np.zeros((6 * P, 6 * P))), b_prior=out.get("b_prior", np.zeros(6 * P)),
+                 lm_marginalised=out.get("lm_marginalised", np.zeros(L, np.uint8)))
+        i, r = LhMargInput(int(marg_pose)), LhMargResult()
+        keep = None
+        if prior is not None:
+            keep = (_as(prior[0], np.float64), _as(prior[1], np.float64))
+            if keep[0].shape != (6 * P, 6 * P) or keep[1].shape != (6 * P,):
+                raise ValueError("prior: H [6P, 6P] and b [6P]")
+            i.prior_H, i.prior_b = _ptr(keep[0]), _ptr(keep[1])
+        r.H_prior, r.b_prior, r.lm_marginalised = _ptr(a["H_prior"]), _ptr(a["b_prior"]), _ptr(a["lm_marginalised"])
+        st = ba_lib().lh_marginalize(self.h, C.byref(i), C.byref(r))
+        a.update(n_landmarks=r.n_landmarks, n_edges=r.n_edges, n_degenerate=r.n_degenerate, bad_row=r.bad_row,
+                 min_pivot=r.min_pivot, max_pivot=r.max_pivot, time_ms=r.time_ms)
+        if st != LH_OK:
+            e = LhError(st, "lh_marginalize")
+            e.result = a
+            raise e
+        if "lm_marginalised" not in out:
+            a["lm_marginalised"] = a["lm_marginalised"].view(bool)
         return a
 
     def solve(self, w, trace_cap=64, reuse=None, outlier_chi2_th=None, want_edges=True):
