@@ -799,6 +799,15 @@ int lh_debug_batch(lh_handle *h, int *batch_max, int *batches, int *retrials);
    controller reads S from one (k_ctrl's LDS layout, k_ctrl_b's band; *n_out 0 otherwise).  *n_out: the doubles the
    buffer holds; *npairs_out: the blocks of S.  LH_E_BADARG without an uploaded window or with cap < *n_out. */
 int lh_debug_reduced_system(lh_handle *h, int which, double *out, int64_t cap, int64_t *n_out, int32_t *npairs_out);
+/* every step of the lambda ladder the last factoring controller of the last solve built, copied behind
+   the handle's stream; nothing on the device is written, so every later solve returns what it would have.  *lad_n_out:
+   the rungs built (1: the step alone; 0: no controller factored, max_iters = 0); dxp_out[cap]: the lad_n pose steps,
+   rung-major (rung r at r 6 n_poses), *n_out = lad_n 6 n_poses; *lad_out: the rung of the pending step (row lad of
+   dxp_out is lh_debug_reduced_system's which = 2); spose_out[r], its_out[r], r < lad_n (room for 16 each): the pose
+   half of rung r's gain denominator and the PCG iterations of its solve (0 under LDL^T).  LH_E_BADARG without an
+   uploaded window or with cap < *n_out: *n_out and *lad_n_out are reported and nothing else is written. */
+int lh_debug_ladder_steps(lh_handle *h, double *dxp_out, int64_t cap, int64_t *n_out, int32_t *lad_n_out,
+                          int32_t *lad_out, double *spose_out, int32_t *its_out);
 
 #ifdef __cplusplus
 }

@@ -1548,6 +1548,34 @@ int lh_debug_reduced_system(lh_handle* h, int which, double* out, int64_t cap, i
     return LH_OK;
 }
 
+// test hook: every step of the lambda ladder the last factoring controller built (include/lego_ba.h), read behind
+// the handle's stream.  It only copies: lh_ctrl, the steps and every later solve are left as they are.
+int lh_debug_ladder_steps(lh_handle* h, double* dxp_out, int64_t cap, int64_t* n_out, int32_t* lad_n_out,
+                          int32_t* lad_out, double* spose_out, int32_t* its_out) {
+    if (!h || !dxp_out || !n_out || !lad_n_out || !lad_out || !spose_out || !its_out) return LH_E_BADARG;
+    if (!h->uploaded) return LH_E_BADARG;
+    if (hipSetDevice(h->device) != hipSuccess) return LH_E_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    // lad, lad_n and the two per-rung arrays (lh_ctrl keeps them in this order: one copy each, device to host)
+    int32_t lad[2] = {0, 0}, its[LH_LAD];
+    double sp[LH_LAD];
+    const char* c = reinterpret_cast<const char*>(h->d_ctrl.p);
+    static_assert(offsetof(lh_ctrl, lad_n) == offsetof(lh_ctrl, lad) + sizeof(int32_t), "lad, lad_n are adjacent");
+    HIPCHK(hipMemcpy(lad, c + offsetof(lh_ctrl, lad), sizeof(lad), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(its, c + offsetof(lh_ctrl, lad_its), sizeof(its), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sp, c + offsetof(lh_ctrl, spose_l), sizeof(sp), hipMemcpyDeviceToHost));
+    const int rungs = std::max(h->cfg.ladder, 1);   // d_dxp holds this many steps (lh_upload)
+    if (lad[1] < 0 || lad[1] > rungs || lad[1] > LH_LAD || lad[0] < 0 || lad[0] >= rungs) return LH_E_STATE;
+    const int64_t n = (int64_t)lad[1] * 6 * (int64_t)h->P;
+    *n_out = n;
+    *lad_n_out = lad[1];
+    if (cap < n) return LH_E_BADARG;
+    if (n > 0) HIPCHK(hipMemcpy(dxp_out, h->d_dxp.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    *lad_out = lad[0];
+    for (int r = 0; r < lad[1]; ++r) { spose_out[r] = sp[r]; its_out[r] = its[r]; }
+    return LH_OK;
+}
+
 int lh_debug_mfma_probe(const double* A, const double* B, double* D) {
     if (lh_launch_mfma_probe(A, B, D) != hipSuccess) return LH_E_HIP;
     if (hipDeviceSynchronize() != hipSuccess) return LH_E_HIP;

@@ -315,6 +315,7 @@ ABI_SYMBOLS = [
     "lh_debug_mfma_probe", "lh_debug_ldlt_probe", "lh_debug_pcg_probe", "lh_debug_event_floor", "lh_debug_stamps",
     "lh_debug_time_lin", "lh_debug_comm_count", "lh_debug_controller", "lh_debug_chains", "lh_debug_ladder",
     "lh_debug_batch", "lh_debug_reduced_system", "lh_debug_lin_shape", "lh_debug_lin_stamps",
+    "lh_debug_ladder_steps",
 ]
 
 _balib = None
@@ -373,6 +374,9 @@ def ba_lib():
         if hasattr(lib, "lh_debug_reduced_system"):
             lib.lh_debug_reduced_system.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                                     C.POINTER(C.c_int32)]
+        if hasattr(lib, "lh_debug_ladder_steps"):
+            lib.lh_debug_ladder_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
         if hasattr(lib, "lh_debug_lin_shape"):
             lib.lh_debug_lin_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         _balib = lib
@@ -998,6 +1002,22 @@ class Solver:
             _check(ba_lib().lh_debug_reduced_system(self.h, int(which), _ptr(out), n.value, C.byref(n),
                                                     C.byref(npairs)), "lh_debug_reduced_system")
         return out, npairs.value
+
+    def ladder_steps(self):
+        """Every step of the lambda ladder the last factoring controller built (lh_debug_ladder_steps):
+        dict(lad_n, lad: the pending step's rung, dxp [lad_n][6 n_poses], spose [lad_n], its [lad_n])."""
+        n, lad_n, lad = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        sp, its = np.zeros(16), np.zeros(16, np.int32)
+        f = ba_lib().lh_debug_ladder_steps
+        st = f(self.h, _ptr(np.zeros(1)), 0, C.byref(n), C.byref(lad_n), C.byref(lad), _ptr(sp), _ptr(its))
+        if st != LH_OK and not (st == LH_E_BADARG and n.value > 0):
+            raise LhError(st, "lh_debug_ladder_steps")
+        out = np.zeros(max(n.value, 1))
+        _check(f(self.h, _ptr(out), n.value, C.byref(n), C.byref(lad_n), C.byref(lad), _ptr(sp), _ptr(its)),
+               "lh_debug_ladder_steps")
+        k = lad_n.value
+        return dict(lad_n=k, lad=lad.value, dxp=out[:n.value].reshape(k, -1) if k else np.zeros((0, 0)),
+                    spose=sp[:k].copy(), its=its[:k].copy())
 
     def comm_count(self):
         """Reduced-system all-reduces the last solve issued (lh_debug_comm_count)."""

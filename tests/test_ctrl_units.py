@@ -40,8 +40,10 @@ def banded_system(P, span, rng):
     return S, pose_first
 
 
-def replay(S, b, units, steps, band=False):
-    """The kernels' blocked LDL^T + solve, driven by the unit table; returns x."""
+def replay(S, b, units, steps, band=False, stale=None):
+    """The kernels' blocked LDL^T + solve, driven by the unit table; returns x.  stale = (t, k): a deliberate
+    fault for tests of a criterion's teeth (tests/test_step_ref_cpu.py) -- the k-th unit of step t reads the
+    operands as they were before step t - 1."""
     n = len(b)
     NE, nb = (n + 15) & ~15, (n + 7) & ~7
     A = np.eye(NE)
@@ -90,6 +92,7 @@ def replay(S, b, units, steps, band=False):
     N, ND, D = factor(0)
     Ns.append(N); NDs.append(ND); Ds.append(D)
     z = np.zeros(NE)
+    older = None
     for t in range(nb // 8):
         k0, m0 = 8 * t, 8 * t + 8
         N, ND = Ns[t], NDs[t]
@@ -108,14 +111,15 @@ def replay(S, b, units, steps, band=False):
             I, jb0, jb1 = g0 + (u & 7), g0 + ((u >> 3) & 7), g0 + ((u >> 6) & 15)
             pending.append((16 * I, 16 * jb0, 16 * jb1, bool(u & STORE)))
         snapshot = A.copy()
-        for rb, j0, j1, st in pending:
+        for k, (rb, j0, j1, st) in enumerate(pending):
             saved = A
-            A = snapshot.copy()
+            A = (older if stale == (t, k) else snapshot).copy()
             before = A.copy()
             tile_row(k0, rb, j0, j1, st, N, ND)
             delta = A - before
             A = saved
             A += delta
+        older = snapshot
         Nn, NDn, Dn = factor(m0)
         Ns.append(Nn); NDs.append(NDn); Ds.append(Dn)
     # x = L^-T z by blocks: x_b = ND_b y_b, then y_r -= sum L[b][r] x_b
